@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- clips/sec (forward + backward + optimizer step) of ORViT-Motionformer 16x224, bf16, on N MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1 launches itself: the parent (which never touches the GPU) spawns one process per GPU through the mirror of the
 reference's launcher (focus_amd/slowfast/utils/misc.py:launch_job -> multiprocessing.run, slowfast/utils/misc.py:285-313)
@@ -10,11 +10,18 @@ the environment) each process joins the group it was given instead.
 
 One step = one pass of the hot path over one synthetic minibatch (batch 8 clips per GPU, 4 boxes/frame):
 build_model(cfg) -> model(inputs, meta) -> label-smoothing CE -> backward (DDP/RCCL all-reduce overlapped) ->
-clip-norm -> AdamW.  Prints ONE JSON line on rank 0 (contract in the task statement), with
+clip-norm -> AdamW.  Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, runs W
+warm-up and K timed steps, and reports them (`ms_per_step` = one timed step); nothing else runs on the GPU.
+
+--dump-outputs DIR writes what the last timed step handed its caller as float32 .npy files (see dump_outputs); the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
+
+--full adds everything else the benchmark measures, after the timed steps:
   roofline     : the dominant kernel (bf16 MFMA GEMM), executed 2*M*N*K FLOPs / HIP-event time, vs 2.5 PF/s
-  cpu_baseline : the CPU oracle (oracle/focus_oracle.py, fp32) timed on this box's host cores on a bounded sample
+  cpu_baseline : the CPU oracle (oracle/focus_oracle.py, fp32) timed on the host's cores on a bounded sample
   steve / hr   : sub-records for BASELINE configs[2] (slot-attention update at B=32,T=24,N=4096,K=11) and the
                  configs[4] shape (16x336, 6 objects, EK heads) on one GPU  (N == 1 only; --workload picks one alone).
+  exposed_allreduce_ms (N > 1): the same K steps again with DDP's reducer switched off.
 """
 import argparse
 import json
@@ -207,6 +214,42 @@ def pmc_traffic(family="gemm_nt_ws_kernel", workload="orvit"):
     return fam["bytes_per_launch"], "%s @ build %s" % (rec["file"], rec.get("head"))
 
 
+DUMP_SAMPLE = 4096                        # elements drawn per parameter (and per gradient) by dump_outputs
+DUMP_LIMIT = 64 << 20                     # bytes, all files together
+
+
+def dump_outputs(path, model, preds, loss):
+    """--dump-outputs: what train_step handed its caller in the last timed step, as float32 .npy files under `path`:
+      logits.npy        [batch, classes]  the model's output
+      loss.npy          [1]               the loss
+      params_sample.npy [n]               DUMP_SAMPLE seeded positions (with replacement) of every parameter after the
+                                          optimizer step, in named_parameters() order (all of a smaller parameter)
+      grads_sample.npy  [n]               the same positions of every parameter's .grad (NaN where it has none)
+    The positions come from a CPU generator seeded 0, so runs with the same arguments sample the same elements."""
+    import numpy as np
+    import torch
+    base = model.module if hasattr(model, "module") else model
+    g = torch.Generator().manual_seed(0)
+    params, grads = [], []
+    with torch.no_grad():
+        for _, p in base.named_parameters():
+            n = p.numel()
+            idx = (torch.randint(0, n, (DUMP_SAMPLE,), generator=g) if n > DUMP_SAMPLE else torch.arange(n)).to(p.device)
+            params.append(p.detach().reshape(-1)[idx].float().cpu())
+            grads.append(p.grad.detach().reshape(-1)[idx].float().cpu() if p.grad is not None
+                         else torch.full((idx.numel(),), float("nan")))
+    arrays = {"logits": preds.detach().float().cpu().numpy(),
+              "loss": loss.detach().float().reshape(1).cpu().numpy(),
+              "params_sample": torch.cat(params).numpy(),
+              "grads_sample": torch.cat(grads).numpy()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # the job every rank runs
 # ----------------------------------------------------------------------------------------------------------------
@@ -241,26 +284,30 @@ def bench_job(cfg):
             torch.cuda.synchronize()
 
         def timed(n, ctx=None):
+            """-> (seconds for n steps, (preds, loss) of the last one)."""
             sync()
             t0 = time.perf_counter()
-            loss = None
+            last = None
             for _ in range(n):
                 if ctx is not None:
                     with ctx():
-                        _, loss = train_step(model, optimizer, loss_fun, inputs, labels, meta, cfg)
+                        last = train_step(model, optimizer, loss_fun, inputs, labels, meta, cfg)
                 else:
-                    _, loss = train_step(model, optimizer, loss_fun, inputs, labels, meta, cfg)
+                    last = train_step(model, optimizer, loss_fun, inputs, labels, meta, cfg)
             sync()
             dt = time.perf_counter() - t0
             if world > 1:
                 tt = torch.tensor([dt], device=dev, dtype=torch.float64)
                 dist.all_reduce(tt, op=dist.ReduceOp.MAX)
                 dt = float(tt.item())
-            return dt, loss
+            return dt, last
 
         for _ in range(a.warmup):
             train_step(model, optimizer, loss_fun, inputs, labels, meta, cfg)
-        dt, loss = timed(a.steps)
+        dt, (preds, loss) = timed(a.steps)
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, model, preds, loss)        # before --full runs more steps on the same model
+        del preds
 
         clips = a.batch * world * a.steps
         value = clips / dt
@@ -279,13 +326,13 @@ def bench_job(cfg):
             "final_loss": round(float(loss.detach()), 4),
         }
         del loss          # no autograd graph of this workload may outlive it (bench_steve captures a HIP graph later)
-        if world > 1:
+        if world > 1 and a.full:
             # exposed (non-overlapped) all-reduce: the same K steps with DDP's reducer switched off
             dt_ns, _ = timed(a.steps, ctx=model.no_sync)
             out["ms_per_step_no_allreduce"] = round(1e3 * dt_ns / a.steps, 3)
             out["exposed_allreduce_ms"] = round(max(0.0, 1e3 * (dt - dt_ns) / a.steps), 3)
 
-        if rank == 0 and not a.no_roofline and not a.fp32:
+        if a.full and rank == 0 and not a.no_roofline and not a.fp32:
             # second pass over the same K steps with HIP events around every launch of the dominant kernel
             ops.GEMM_TIMING = []
             for _ in range(a.steps):
@@ -333,12 +380,12 @@ def bench_job(cfg):
                                "weight_grad_kernel": {"kernel": "bf16 TN GEMM (gemm_mfma_tn_ws.hip, gemm_mfma_tn.hip)",
                                                       "achieved": round(tn_tf, 2),
                                                       "ms_per_step": round(tn_ms / max(a.steps, 1), 3)}}
-        elif world > 1 and not a.no_roofline and not a.fp32:
+        elif a.full and world > 1 and not a.no_roofline and not a.fp32:
             for _ in range(a.steps):       # keep ranks in lock-step with rank 0's instrumented pass
                 train_step(model, optimizer, loss_fun, inputs, labels, meta, cfg)
             torch.cuda.synchronize()
 
-        if rank == 0 and world == 1 and not a.no_cpu_baseline:
+        if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(model, cfg)
             except Exception as e:  # the baseline is a reported figure; never lose the bench line to it
@@ -348,7 +395,7 @@ def bench_job(cfg):
         ops.drop_caches()
         torch.cuda.empty_cache()
 
-    if world == 1 and a.workload in ("steve", "all") and not a.fp32:
+    if a.full and world == 1 and a.workload in ("steve", "all") and not a.fp32:
         rec = _guard(lambda: bench_steve(a, dev))
         if a.steve_model_batch > 0 and not a.steve_eager:
             import torch as _t
@@ -358,7 +405,7 @@ def bench_job(cfg):
             out = rec
         else:
             out["steve"] = rec
-    if world == 1 and a.workload in ("hr", "all") and not a.fp32:
+    if a.full and world == 1 and a.workload in ("hr", "all") and not a.fp32:
         rec = _guard(lambda: bench_hr(a, dev))
         if out is None:
             out = rec
@@ -648,13 +695,18 @@ def main(argv=None, job=None):
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=8, help="clips per GPU")
     ap.add_argument("--workload", default="all", choices=["all", "orvit", "steve", "hr"],
-                    help="all = the headline ORViT-MF line with the steve / hr sub-records (N == 1)")
+                    help="all = the headline ORViT-MF line, with the steve / hr sub-records under --full (N == 1); "
+                         "steve / hr alone need --full")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other measurement: roofline, cpu_baseline, steve / hr, exposed all-reduce")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32)")
     ap.add_argument("--steve-batch", type=int, default=32)
     ap.add_argument("--hr-batch", type=int, default=4)
     ap.add_argument("--hr-large-batch", type=int, default=16, help="second HR fp8 record at this batch (0: skip)")
     ap.add_argument("--fp32", action="store_true", help="TRAIN.MIXED_PRECISION False (precision path)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--gemm-shapes", action="store_true", help="print per-shape GEMM timings to stderr")
+    ap.add_argument("--gemm-shapes", action="store_true", help="print per-shape GEMM timings to stderr (needs --full)")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--steve-eager", action="store_true", help="time the STEVE sub-record eagerly (no HIP graph)")
     ap.add_argument("--steve-model-batch", type=int, default=16,
@@ -666,6 +718,16 @@ def main(argv=None, job=None):
     args = ap.parse_args(argv)
     if args.same_device and args.backend == "nccl":
         raise SystemExit("--same-device needs --backend gloo")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if not args.full and args.workload in ("steve", "hr"):
+        raise SystemExit("--workload %s is a --full measurement: add --full" % args.workload)
+    if not args.full and args.gemm_shapes:
+        raise SystemExit("--gemm-shapes comes from the --full roofline pass: add --full")
+    if args.dump_outputs is not None:
+        if args.workload in ("steve", "hr"):
+            raise SystemExit("--dump-outputs writes the ORViT-MF step's outputs: use --workload orvit or all")
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
 
     env_world = os.environ.get("WORLD_SIZE")
     n = int(env_world) if env_world is not None else max(args.gpus, 1)

@@ -13,9 +13,10 @@
 // The unit list (built once per shape signature by focus_linear_wgrad_group_plan, kept on the device by the caller) walks
 // every problem's tile grid in blocks of 4 x 8 tiles and every XCD owns a contiguous band of the list (~one block): the
 // ~29 units that share an L2 read 4 dY panels and 8 X panels between them.  (First version: tile_j fastest over whole
-// rows -- PMC FETCH 720 MB per launch against ~250 MB of operands: every XCD streamed most X panels.)  Bias gradients ride on the matrix pipe as ones^T . dY (unit
-// tile_j takes the K-steps kt = tile_j mod tiles_j) and are ADDED to db with fp32 atomics (a few thousand per launch);
-// db is zeroed by the caller's memset.
+// rows -- PMC FETCH 720 MB per launch against ~250 MB of operands: every XCD streamed most X panels.)  Bias gradients ride on the matrix pipe as ones^T . dY:
+// the unit of tile_j == 0 of every row of tiles sums ALL K-steps in order and stores db (2 more MFMAs per 16 in that unit
+// only).  No atomics: the sums, like dW, are the same bits on every run.  (Dealing the K-steps over the tiles_j units
+// and adding their partials to db with fp32 atomics made db differ in the last bits from run to run.)
 #include "focus_common.h"
 #include "gemm_internal.h"
 #include <algorithm>
@@ -82,7 +83,7 @@ __global__ __launch_bounds__(64 * (BI * BJ / 4096 + NLOAD)) void gemm_tn_group_k
     const int my_units = jwg < band_n ? (band_n - jwg + gx - 1) / gx : 0;
     if (my_units == 0) return;
 
-    struct Unit { const bf16_t* P; const bf16_t* Q; float* C; float* db; int64_t ldp, ldq; int I, J, Mred, i0, j0, nk, valid_last, tj, tiles_j; };
+    struct Unit { const bf16_t* P; const bf16_t* Q; float* C; float* db; int64_t ldp, ldq; int I, J, Mred, i0, j0, nk, valid_last, tj; };
     auto unit_of = [&](int i) __attribute__((always_inline)) {
         const UnitRec ur = units[band0 + jwg + i * gx];
         const int pi = __builtin_amdgcn_readfirstlane((int)ur.prob);
@@ -96,7 +97,6 @@ __global__ __launch_bounds__(64 * (BI * BJ / 4096 + NLOAD)) void gemm_tn_group_k
         t.i0 = __builtin_amdgcn_readfirstlane((int)ur.ti) * BI;
         t.tj = __builtin_amdgcn_readfirstlane((int)ur.tj);
         t.j0 = t.tj * BJ;
-        t.tiles_j = p.tiles_j;
         t.nk = (p.Mred + BKM - 1) / BKM;
         t.valid_last = p.Mred - (t.nk - 1) * BKM;
         return t;
@@ -206,17 +206,15 @@ __global__ __launch_bounds__(64 * (BI * BJ / 4096 + NLOAD)) void gemm_tn_group_k
         for (int a = 0; a < 4; ++a)
 #pragma unroll
             for (int b = 0; b < 4; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        const bool want_b = cur.db != nullptr;
-        int cs_in = cur.tj;                                // steps until this unit's next column-sum K-step
+        const bool want_b = cur.db != nullptr && cur.tj == 0;     // this unit owns the bias sums of its row of tiles
 #pragma unroll
         for (int n = 0; n < NA; ++n) accb[n] = (f32x4){0.f, 0.f, 0.f, 0.f};
         for (int kt = 0; kt + 1 < cur.nk; ++kt) {
-            compute(smem + st * STAGE, std::false_type{}, BKM, want_b && cs_in == 0);
-            cs_in = cs_in == 0 ? cur.tiles_j - 1 : cs_in - 1;
+            compute(smem + st * STAGE, std::false_type{}, BKM, want_b);
             st = st == 2 ? 0 : st + 1;
             __builtin_amdgcn_s_barrier();                  // end of this K-step
         }
-        compute(smem + st * STAGE, std::true_type{}, cur.valid_last, want_b && cs_in == 0);
+        compute(smem + st * STAGE, std::true_type{}, cur.valid_last, want_b);
         st = st == 2 ? 0 : st + 1;
         __builtin_amdgcn_s_barrier();
         // acc[a][b][r4] = D[j = j0 + wj*64 + b*16 + fq*4 + r4][i = i0 + wi*64 + a*16 + fr]: straight from the registers
@@ -224,7 +222,7 @@ __global__ __launch_bounds__(64 * (BI * BJ / 4096 + NLOAD)) void gemm_tn_group_k
 #pragma unroll
             for (int n = 0; n < NA; ++n) {
                 const int gi = cur.i0 + wi * 64 + (wj * NA + n) * 16 + fr;
-                if (gi < cur.I) atomicAdd(cur.db + gi, accb[n][0]);
+                if (gi < cur.I) cur.db[gi] = accb[n][0];
             }
         }
 #pragma unroll
@@ -273,8 +271,8 @@ extern "C" int focus_linear_wgrad_group_plan(const focus_wgrad_item* items, int 
     return n == total ? FOCUS_OK : FOCUS_ERR_SHAPE;
 }
 
-// `items` is a HOST array of at most 8 problems (longest reduction first gives the best balance); every db must have been
-// zeroed by the caller (the bias gradients are accumulated with atomics); dW is written densely ([N, K], row stride K).
+// `items` is a HOST array of at most 8 problems (longest reduction first gives the best balance); dW is written densely
+// ([N, K], row stride K) and db (when given) is stored whole: neither needs zeroing.
 // dev_units: DEVICE copy of the list focus_linear_wgrad_group_plan made for the same (N, K) sequence.
 extern "C" int focus_linear_wgrad_group(const focus_wgrad_item* items, int n_items, const void* dev_units, void* stream) {
     if (!items || !dev_units) return FOCUS_ERR_NULL;

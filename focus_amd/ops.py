@@ -635,9 +635,7 @@ def _group_flush(grp, stash):
     dev = probs[0][2].device
     nw = sum(t[2].shape[1] * t[3].shape[1] for t in probs)
     nb = sum(t[2].shape[1] for t in probs if t[1] >= 0)
-    flat = torch.empty(nw + nb, device=dev, dtype=torch.float32)
-    if nb:
-        flat[nw:].zero_()                                    # the bias sums are accumulated with atomics
+    flat = torch.empty(nw + nb, device=dev, dtype=torch.float32)      # the launch stores every dW and db element
     ow, ob = 0, nw
     for n, (wi, bi, dy2, x2) in enumerate(probs):
         M, N = dy2.shape

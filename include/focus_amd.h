@@ -399,8 +399,8 @@ typedef struct focus_fp8_item {
 int focus_fp8_refresh(const focus_fp8_item* items, int n_items, int max_rows, int max_cols, void* amax_scratch, void* stream);
 
 /* Weight and bias gradients of up to 8 nn.Linear layers in ONE launch (gemm_tn_group.hip; autograd of attention.py:506,
- * 536,555 and common.py:26-34 inside one block): dw_p[N,K] = dy_p[M,N]^T . x_p[M,K] (fp32, dense), db_p[N] += column sums
- * of dy_p (fp32 atomics: the caller zeroes db; NULL = no bias).  bf16 operands, row strides ld_dy / ld_x in elements;
+ * 536,555 and common.py:26-34 inside one block): dw_p[N,K] = dy_p[M,N]^T . x_p[M,K] (fp32, dense), db_p[N] = column sums
+ * of dy_p (stored in a fixed order, no atomics: bitwise reproducible; NULL = no bias).  bf16 operands, row strides ld_dy / ld_x in elements;
  * N, K, strides multiples of 8; 16-byte aligned pointers.  `items` is a HOST array. */
 typedef struct focus_wgrad_item {
     const void* dy; const void* x; float* dw; float* db;

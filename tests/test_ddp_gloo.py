@@ -103,10 +103,17 @@ def _bench_main(argv, extra):
         cfg.EXTRA = CfgNode(extra)
         return cfg
     bench.make_cfg = make_cfg
+    same_device = os.environ.get("FOCUS_SAME_DEVICE")
     try:
-        return bench.main(argv, job=_standin_with_extra)
+        # --same-device: on a host with a GPU every rank binds cuda:0 (the stand-in job computes on the CPU), so the
+        # launch path does not depend on how many GPUs the host has; without a GPU it changes nothing
+        return bench.main(argv + ["--same-device"], job=_standin_with_extra)
     finally:
         bench.make_cfg = orig
+        if same_device is None:
+            os.environ.pop("FOCUS_SAME_DEVICE", None)
+        else:
+            os.environ["FOCUS_SAME_DEVICE"] = same_device
 
 
 def _standin_with_extra(cfg):

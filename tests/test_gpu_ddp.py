@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 
 def test_bench_two_ranks_same_device_gloo():
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--same-device",
-           "--steps", "2", "--warmup", "1", "--batch", "1", "--no-cpu-baseline", "--no-roofline", "--workload", "orvit"]
+           "--steps", "2", "--warmup", "1", "--batch", "1", "--full", "--no-cpu-baseline", "--no-roofline", "--workload", "orvit"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-4000:]
     line = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]

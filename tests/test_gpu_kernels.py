@@ -446,7 +446,8 @@ def test_grouped_weight_gradients_match_fp64(rows):
     """Five Linears of a Motionformer block + a bias-free one with a longer reduction and ragged sizes: the grouped launch
     against fp64 dY^T.X / column sums of the same bf16 values.  One fp32 accumulator per output element runs through the WHOLE
     reduction (no split): the bound is the classical one for a length-M fp32 chain, |err| <= 2e-6 * sum_m |dy||x| (M 2^-24 in
-    the worst case; a dropped K-step of 64 rows would be 400x that)."""
+    the worst case; a dropped K-step of 64 rows would be 400x that).  dW and db start as NaN (both are stored whole, no
+    zeroing needed) and a second launch reproduces them bit for bit (no atomics)."""
     import ctypes
     from focus_amd import _lib
     d = dev()
@@ -461,7 +462,7 @@ def test_grouped_weight_gradients_match_fp64(rows):
         dy = bf(torch.randn(M, N + 8, device=d, generator=g))[:, :N]          # a strided view: ld_dy = N + 8
         x = bf(torch.randn(M, K, device=d, generator=g))
         dw = torch.full((N, K), float("nan"), device=d)
-        db = torch.zeros(N, device=d) if hb else None
+        db = torch.full((N,), float("nan"), device=d) if hb else None
         keep.append((dy, x, dw, db))
         arr[n].dy, arr[n].x, arr[n].dw = dy.data_ptr(), x.data_ptr(), dw.data_ptr()
         arr[n].db = db.data_ptr() if hb else None
@@ -483,6 +484,16 @@ def test_grouped_weight_gradients_match_fp64(rows):
         if db is not None:
             ck.tight(db, dy.double().sum(0), "db %d" % n, rtol=2e-6, floor=0.0, mag=dy.double().abs().sum(0))
     ck.done()
+    first = [(dw.clone(), None if db is None else db.clone()) for _, _, dw, db in keep]
+    for _, _, dw, db in keep:
+        dw.fill_(float("nan"))
+        if db is not None:
+            db.fill_(float("nan"))
+    _lib.check(L.focus_linear_wgrad_group(arr, len(shapes), ctypes.c_void_p(table.data_ptr()), stream), "linear_wgrad_group")
+    torch.cuda.synchronize()
+    for n, ((_, _, dw, db), (dw0, db0)) in enumerate(zip(keep, first)):
+        assert torch.equal(dw, dw0), "dW %d differs between two launches" % n
+        assert db is None or torch.equal(db, db0), "db %d differs between two launches" % n
 
 
 def test_wgrad_group_context_equals_ungrouped():

@@ -1,4 +1,4 @@
-"""One-screen summary of a bench.py JSON line.   python tools/bench_summary.py [file=profiles/r03_bench.json]"""
+"""One-screen summary of a `bench.py --full` JSON line.   python tools/bench_summary.py [file=profiles/r03_bench.json]"""
 import json
 import sys
 

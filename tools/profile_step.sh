@@ -10,7 +10,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 HEAD=$(cat "$ROOT/focus_amd/lib/BUILD_HEAD" 2>/dev/null || echo unknown)
 STEPS=3; WARM=1
-ARGS="bench.py --workload $WL --steps $STEPS --warmup $WARM --no-cpu-baseline --no-roofline"
+ARGS="bench.py --workload $WL --steps $STEPS --warmup $WARM --full --no-cpu-baseline --no-roofline"
 # the STEVE record is traced eagerly: warm-up + timed steps = STEPS + WARM executions of the step, nothing else
 [ "$WL" = steve ] && ARGS="$ARGS --steve-eager"
 [ "$WL" = hr ] && ARGS="$ARGS --hr-large-batch 0"
