@@ -21,3 +21,5 @@ int focus_gemm_mfma_tn_ws(const focus_gemm_desc& d, const focus_tn_plan& pl, flo
 // small row counts (M <= 1024, K <= 1536): one 32x32 tile per workgroup, in-workgroup split-K, operands in registers
 bool focus_gemm_mfma_small_ok(const focus_gemm_desc& d);
 int focus_gemm_mfma_small(const focus_gemm_desc& d, hipStream_t s);
+// records the kernel family for focus_gemm_last_kernel() (entry points outside focus_gemm(): focus_gemm_mx)
+void focus_gemm_note_kernel(int kind);

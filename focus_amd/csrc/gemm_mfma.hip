@@ -412,6 +412,7 @@ bool focus_gemm_mfma_nt_ok(const focus_gemm_desc& d) {
 // which kernel family the last focus_gemm() on this thread dispatched to (bench.py attributes its per-launch timings)
 static thread_local int g_last_kernel = FOCUS_GEMM_KERNEL_GENERIC;
 extern "C" int focus_gemm_last_kernel(void) { return g_last_kernel; }
+void focus_gemm_note_kernel(int kind) { g_last_kernel = kind; }
 
 int focus_gemm_mfma_nt(const focus_gemm_desc& d, hipStream_t s) {
     if (!focus_gemm_mfma_nt_ok(d)) return FOCUS_ERR_ALIGN;

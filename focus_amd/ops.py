@@ -421,6 +421,91 @@ def shadow_fp8(w, transposed=False):
     return (e[3] if transposed else e[2]), e[4]
 
 
+# --------------------------------------------------------------------------------------------------
+# MX e4m3 activations (TRAIN.FP8_ACTIVATIONS): the forward GEMMs of the fp8-weight Linears also take their INPUT in
+# e4m3, with one power-of-two (E8M0) scale per 32 consecutive elements of a row (csrc/mx_quant.hip), and run the scaled
+# fp8 MFMA (csrc/gemm_mx_fp8.hip).  `with ops.fp8_activations(True):` inside ops.fp8_weights(True) turns it on.  The
+# quantiser is a straight-through identity: the backward of _LinearFn / _MlpFn is the fp8-weight backward (dX on the
+# e4m3 weights, dW = dY^T X with the saved bf16 X); no fp8 tensor is saved.
+# --------------------------------------------------------------------------------------------------
+FP8_ACTIVATIONS = False
+
+
+class fp8_activations:
+    def __init__(self, on=True):
+        self.on = bool(on)
+
+    def __enter__(self):
+        global FP8_ACTIVATIONS
+        self.prev = FP8_ACTIVATIONS
+        FP8_ACTIVATIONS = self.on
+        return self
+
+    def __exit__(self, *exc):
+        global FP8_ACTIVATIONS
+        FP8_ACTIVATIONS = self.prev
+        return False
+
+
+def mx_ok(w, rows, dtype):
+    """The MX GEMM takes this Linear: the fp8-weight path does, and K is a whole number of 128-element K-steps."""
+    return fp8_ok(w, rows, dtype) and getattr(w, "_focus_base", w).shape[1] % 128 == 0
+
+
+def mx_quantize(x):
+    """bf16 x [M,K] (K % 32 == 0) -> (e4m3 codes [M,K] uint8, E8M0 scales [M, K/32] uint8 in rows padded to 4 bytes)."""
+    _need_gpu(x)
+    if x.dtype != torch.bfloat16 or x.dim() != 2:
+        raise RuntimeError("focus_amd: mx_quantize takes a 2-D bfloat16 tensor")
+    if x.stride(1) != 1:
+        x = x.contiguous()
+    M, K = x.shape
+    codes = torch.empty(M, K, dtype=torch.uint8, device=x.device)
+    scales = torch.empty(M, -(-(K // 32) // 4) * 4, dtype=torch.uint8, device=x.device)[:, :K // 32]
+    _lib.check(_lib.lib().focus_mx_quant(_p(x), x.stride(0), M, K, BF16, _p(codes), codes.stride(0), _p(scales),
+                                         scales.stride(0), _stream()), "mx_quant")
+    return codes, scales
+
+
+def mm_nt_mx(xq, xs, wq, w_scale, bias=None, residual=None, aux=None, epilogue=EPI_NONE, alpha=1.0):
+    """bf16 [M,N] = epi(alpha * w_scale * (dec(xq) 2^(xs - 127)) . dec(wq)^T + bias) + residual: xq, xs from mx_quantize,
+    wq [N,K] e4m3 weight codes with the per-tensor device scalar w_scale (shadow_fp8)."""
+    M, K = xq.shape
+    N = wq.shape[0]
+    c = torch.empty(M, N, device=xq.device, dtype=torch.bfloat16)
+    d = GemmDesc()
+    d.M, d.N, d.K = M, N, K
+    d.batch0, d.batch1 = 1, 1
+    d.A, d.rsA, d.csA = xq.data_ptr(), xq.stride(0), xq.stride(1)
+    d.B, d.rsB, d.csB = wq.data_ptr(), wq.stride(1), wq.stride(0)
+    d.C, d.rsC, d.csC = c.data_ptr(), N, 1
+    d.bias = bias.data_ptr() if bias is not None else None
+    d.residual = residual.data_ptr() if residual is not None else None
+    d.aux = aux.data_ptr() if aux is not None else None
+    d.alpha = alpha
+    d.epilogue = epilogue
+    d.dtype_ab = d.dtype_b = _lib.FP8_E4M3
+    d.dtype_c = BF16
+    d.b_scale = w_scale.data_ptr()
+    if GEMM_TIMING is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    _lib.check(_lib.lib().focus_gemm_mx(ctypes.byref(d), _p(xs), xs.stride(0), _stream()), "gemm_mx")
+    if GEMM_TIMING is not None:
+        e1.record()
+        GEMM_TIMING.append((2.0 * M * N * K, e0, e1, "nt_mx", (M, N, K, 1, epilogue)))
+    return c
+
+
+def _mm_fp8(x2, w, bias=None, residual=None, aux=None, epilogue=EPI_NONE, alpha=1.0):
+    """Forward product of an fp8-weight Linear: MX activations when the key is on and the shape qualifies, else bf16."""
+    wq, sc = shadow_fp8(w)
+    if FP8_ACTIVATIONS and mx_ok(w, x2.shape[0], x2.dtype):
+        xq, xs = mx_quantize(x2)
+        return mm_nt_mx(xq, xs, wq, sc, bias=bias, residual=residual, aux=aux, epilogue=epilogue, alpha=alpha)
+    return mm_nt(x2, wq, bias=bias, residual=residual, aux=aux, epilogue=epilogue, alpha=alpha, b_scale=sc)
+
+
 def _dx_from(dy, w, dtype, aux=None, epilogue=EPI_NONE, alpha=1.0, fp8=False):
     """alpha * dy [M,N] . w[N,K] -> [M,K].  fp8: the forward multiplied by the e4m3 copy of w, so does this."""
     if fp8:
@@ -748,8 +833,7 @@ class _LinearFn(torch.autograd.Function):
         r2 = residual.reshape(-1, w.shape[0]).contiguous() if residual is not None else None
         ctx.fp8 = fp8_ok(w, x2.shape[0], x.dtype)
         if ctx.fp8:
-            wq, sc = shadow_fp8(w)
-            y = mm_nt(x2, wq, bias=b, residual=r2, alpha=alpha, b_scale=sc)
+            y = _mm_fp8(x2, w, bias=b, residual=r2, alpha=alpha)
         else:
             y = mm_nt(x2, shadow(w, x.dtype), bias=b, residual=r2, alpha=alpha)
         ctx.save_for_backward(x2, w)
@@ -909,9 +993,8 @@ class _MlpFn(torch.autograd.Function):
         ctx.fp8 = fp8_ok(w1, M, x.dtype) and fp8_ok(w2, M, x.dtype)
         r2 = residual.reshape(-1, w2.shape[0]).contiguous() if residual is not None else None
         if ctx.fp8:
-            (q1, s1), (q2, s2) = shadow_fp8(w1), shadow_fp8(w2)
-            a = mm_nt(x2, q1, bias=b1, aux=z, epilogue=act, b_scale=s1)
-            y = mm_nt(a, q2, bias=b2, residual=r2, b_scale=s2)
+            a = _mm_fp8(x2, w1, bias=b1, aux=z, epilogue=act)
+            y = _mm_fp8(a, w2, bias=b2, residual=r2)
         else:
             a = mm_nt(x2, shadow(w1, x.dtype), bias=b1, aux=z, epilogue=act)
             y = mm_nt(a, shadow(w2, x.dtype), bias=b2, residual=r2)

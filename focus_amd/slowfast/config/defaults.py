@@ -161,6 +161,7 @@ def _defaults():
     C.DDP_BF16_GRADS = False     # build-owned: bf16 gradient buckets on the wire (focus_amd/parallel.py)
     C.SLOTS.GRAPH_SLOT_UPDATE = False   # build-owned: replay the slot update from captured HIP graphs inside the training step
     C.TRAIN.FP8_WEIGHTS = False  # build-owned (BASELINE configs[4]): OCP e4m3 working copies of the Linear weights, bf16 activations
+    C.TRAIN.FP8_ACTIVATIONS = False  # build-owned: with FP8_WEIGHTS, MX e4m3 activations (scale per 32 elements) for the block Linears' forward GEMMs
     return C
 
 

@@ -130,14 +130,17 @@ class ORViT(nn.Module):
         # (O = 4 times fewer rows than the RoI cells), the crops are sampled in dim/2 channels (half the gather bytes, half
         # the crop tensor, half the RoIAlign backward) with the ReLU fused into the sampling kernels; only the second
         # Linear runs on the RoI cells.  Same values up to rounding order.
+        # With TRAIN.FP8_ACTIVATIONS patch_to_d keeps bf16 activations (fp8 weights only): applied before RoIAlign, its input
+        # is not a tensor the reference's Linear ever sees, so quantising it would not be the reference's quantisation.
         p2d = self.patch_to_d
-        if _COMMUTE_PATCH_TO_D:
-            z = ops.linear(x, p2d[0].weight)                                                 # [BS, 1+T*HW, d/2]
-            crops = self.crop_layer.crop_stream(z, box_tensors, T, H, W, relu=True)         # [BS*T*O, HW, d/2]
-            pre = ops.linear(crops, p2d[2].weight)                                           # last ReLU commutes with max
-        else:                                                                                # the reference's order (:135-137)
-            crops = self.crop_layer.crop_stream(x, box_tensors, T, H, W)                    # [BS*T*O, HW, d]
-            pre = ops.mlp(crops, p2d[0].weight, None, p2d[2].weight, None, act=ops.EPI_RELU)
+        with ops.fp8_activations(False):
+            if _COMMUTE_PATCH_TO_D:
+                z = ops.linear(x, p2d[0].weight)                                             # [BS, 1+T*HW, d/2]
+                crops = self.crop_layer.crop_stream(z, box_tensors, T, H, W, relu=True)     # [BS*T*O, HW, d/2]
+                pre = ops.linear(crops, p2d[2].weight)                                       # last ReLU commutes with max
+            else:                                                                            # the reference's order (:135-137)
+                crops = self.crop_layer.crop_stream(x, box_tensors, T, H, W)                # [BS*T*O, HW, d]
+                pre = ops.mlp(crops, p2d[0].weight, None, p2d[2].weight, None, act=ops.EPI_RELU)
         obj = torch.relu(ops.cell_amax(pre)).view(BS, T, O, d)
         box_emb = _relu_pair(self.c_coord_to_feature, box_tensors, x.dtype)
         obj = obj + self.box_categories.to(x.dtype) + box_emb                               # :141-143

@@ -47,6 +47,12 @@ class Motionformer(nn.Module):
         # build-owned key (BASELINE configs[4]): the Linear weights of the blocks are multiplied as OCP e4m3 copies with one
         # scale per tensor, activations stay bf16 (focus_amd.ops.fp8_weights); needs the bf16 compute dtype
         self.fp8_weights = bool(cfg.TRAIN.get("FP8_WEIGHTS", False)) and cfg.TRAIN.MIXED_PRECISION
+        # build-owned key: the forward GEMMs of those Linears also take MX e4m3 activations (one power-of-two scale per 32
+        # elements, focus_amd.ops.fp8_activations); only on top of FP8_WEIGHTS, off under fp32 like it
+        if cfg.TRAIN.get("FP8_ACTIVATIONS", False) and not cfg.TRAIN.get("FP8_WEIGHTS", False):
+            raise ValueError("TRAIN.FP8_ACTIVATIONS needs TRAIN.FP8_WEIGHTS: the MX GEMM multiplies e4m3 activations by the "
+                             "e4m3 weight copies")
+        self.fp8_activations = bool(cfg.TRAIN.get("FP8_ACTIVATIONS", False)) and self.fp8_weights
 
         k = [cfg.MF.PATCH_SIZE_TEMP, self.patch_size, self.patch_size]
         self.patch_embed_3d = stem_helper.PatchEmbed(dim_in=self.in_chans, dim_out=self.embed_dim, kernel=k, stride=k,
@@ -150,7 +156,7 @@ class Motionformer(nn.Module):
             x = self.pos_drop(x)
         side = int(npatch ** 0.5)
         thw = [self.temporal_resolution, side, side]
-        with ops.fp8_weights(self.fp8_weights):
+        with ops.fp8_weights(self.fp8_weights), ops.fp8_activations(self.fp8_activations):
             for blk in self.blocks:
                 x, _ = blk(x, metadata, thw)
         n = self.norm

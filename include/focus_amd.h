@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-enum focus_dtype { FOCUS_F32 = 0, FOCUS_BF16 = 1, FOCUS_FP8_E4M3 = 2 /* OCP e4m3fn codes: weights (B operand) only */ };
+enum focus_dtype { FOCUS_F32 = 0, FOCUS_BF16 = 1, FOCUS_FP8_E4M3 = 2 /* OCP e4m3fn codes: weights (B of focus_gemm), or both operands of focus_gemm_mx */ };
 
 enum focus_status {
     FOCUS_OK = 0,
@@ -88,13 +88,31 @@ enum focus_gemm_kernel {
     FOCUS_GEMM_KERNEL_NT = 1,        /* gemm_mfma.hip uniform 128x128 (few tiles, split-K)          */
     FOCUS_GEMM_KERNEL_NT_WS = 2,     /* gemm_mfma_ws.hip wave-specialised (the step's dominant kernel) */
     FOCUS_GEMM_KERNEL_TN = 3,        /* gemm_mfma_tn*.hip (weight gradients)                        */
-    FOCUS_GEMM_KERNEL_NT_SMALL = 4   /* gemm_mfma_small.hip (M <= 1024 rows: recurrent / motion-stream Linears) */
+    FOCUS_GEMM_KERNEL_NT_SMALL = 4,  /* gemm_mfma_small.hip (M <= 1024 rows: recurrent / motion-stream Linears) */
+    FOCUS_GEMM_KERNEL_NT_MX = 5      /* gemm_mx_fp8.hip (focus_gemm_mx: MX-scaled e4m3 activations x e4m3 weights) */
 };
 int focus_gemm_last_kernel(void);
 
 /* Tuning hook: force the row-tile height of the wave-specialised NT kernel (128 or 192; 0 = automatic choice by the
  * modelled rounds-x-tile-time cost).  Used by tools/gemm_tile_ab.py for A/B timing inside one process. */
 int focus_gemm_tile_override(int bm);
+
+/* MX e4m3 activations (TRAIN.FP8_ACTIVATIONS): x [rows, cols] bf16 -> codes [rows, cols] OCP e4m3 + scales
+ * [rows, cols / 32] E8M0, one per block of 32 consecutive elements of a row.  Block amax = 1.m x 2^E:
+ * e = E - 8 + (m > 0.75) (the smallest e with amax <= 448 x 2^e), clamped to [-127, 127], -127 for an all-zero block;
+ * scale byte = e + 127, 0xFF for a block holding a NaN or an Inf (its codes are unspecified); code = RNE_e4m3(x * 2^-e)
+ * in fp32.  dtype must be FOCUS_BF16; cols % 32 == 0; strides in elements (x) and bytes (codes, scales): ldx % 8,
+ * ld_codes % 16, ld_scales % 4 == 0; x and codes 16-byte, scales 4-byte aligned. */
+int focus_mx_quant(const void* x, int64_t ldx, int rows, int cols, int dtype, void* codes, int64_t ld_codes, void* scales,
+                   int64_t ld_scales, void* stream);
+
+/* MX-scaled fp8 NT GEMM (gemm_mx_fp8.hip, v_mfma_scale_f32_16x16x128_f8f6f4):
+ *   C = epi(alpha * b_scale * sum_k dec(A[m,k]) 2^(a_scales[m, k/32] - 127) dec(B[k,n]) + bias) [+ residual]
+ * A: focus_mx_quant codes [M,K] (dtype_ab = FOCUS_FP8_E4M3, csA = 1, rsA % 16 == 0); a_scales: its E8M0 bytes
+ * [M, K/32] at row stride ld_a_scales (bytes, % 4 == 0); B: e4m3 weight codes given as [N,K] rows (dtype_b =
+ * FOCUS_FP8_E4M3, rsB = 1, csB % 16 == 0) with the per-tensor DEVICE scalar b_scale; C, residual, aux bf16 (csC = 1).
+ * batch 1, N % 64 == 0, K % 128 == 0, any M; epilogue NONE, GELU (pre-activation to aux if given) or RELU. */
+int focus_gemm_mx(const focus_gemm_desc* desc, const void* a_scales, int64_t ld_a_scales, void* stream);
 
 /* Weight-gradient form (A strided along the reduction: rsA == 1, csB == 1, bf16 in, fp32 out): the long reduction is
  * split over workgroups.  With desc->aux == NULL the partial sums are added to a zero-initialised C with fp32
