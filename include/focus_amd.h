@@ -49,6 +49,10 @@ int focus_abi_version(void);
  * element strides (rs = row stride, cs = column stride) and a two-level batch (batch0 x batch1).
  * The MFMA path is taken when dtype is bf16 and both A and B are contiguous along K (csA==1,
  * rsB==1), 16-byte aligned; everything else runs the generic tiled kernel.
+ * Degenerate sizes (pinned by tests/test_gpu_gemm_desc.py): M <= 0 or N <= 0 returns FOCUS_OK without a launch and
+ * leaves C and aux alone; K == 0 is an empty sum, C = epi(bias) [+ residual] [+ C] (generic kernel; with GELU the
+ * pre-activation saved in aux is the bias); K < 0 is FOCUS_ERR_SHAPE.  Nothing outside the batch0 x batch1 windows
+ * of M x N elements of C (and of aux, for GELU) is written.
  * ----------------------------------------------------------------------------------------------*/
 enum focus_epilogue {
     FOCUS_EPI_NONE = 0,

@@ -6,6 +6,8 @@ Here every kernel is fed bf16-ROUNDED inputs and compared with an fp64 evaluatio
 element:   |got - want| <= rtol * max(|want|, floor * max|want|)   with rtol = 2^-7 (two bf16 ulps) for single-kernel
 outputs; the only slack is the output's own bf16 rounding (2^-9) and the bf16 rounding of MFMA operands the kernel forms
 internally (probabilities, dL).  A wrong tail mask, swizzle or epilogue lands far outside that."""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -69,6 +71,9 @@ def dgelu64(v):
 # ----------------------------------------------------------------------------------------------------------------
 BENCH_SHAPES = [(12552, 768, 768), (12552, 2304, 768), (12552, 3072, 768), (12552, 768, 3072), (100352, 768, 768)]
 RAGGED_SHAPES = [(1601, 768, 768), (333, 200, 192), (12808, 1536, 768), (129, 97, 64), (6272, 384, 768)]
+# dispatch switches read once per process: with one of them set the kernel family is reported, not asserted
+GEMM_SWITCHES = ("FOCUS_GEMM_WS", "FOCUS_GEMM_SMALL", "FOCUS_GEMM_TN", "FOCUS_GEMM_LDS_EPI", "FOCUS_GEMM_SMALL_PASSES",
+                 "FOCUS_GEMM_TILE")
 # few rows: gemm_mfma_small.hip (the recurrent STEVE Linears at B*K = 352 rows, the motion stream at 256, ragged edges)
 SMALL_SHAPES = [(352, 192, 192), (352, 576, 192), (352, 192, 768), (352, 768, 192), (256, 768, 1536), (45, 72, 64),
                 (1000, 40, 128), (17, 8, 1536),
@@ -103,7 +108,16 @@ def test_nt_gemm_epilogues(shape):
     # gelu(round(z)) rounded again: (|z gelu'(z)| + |gelu(z)|) u <= 2.3 u |gelu(z)| for z > 0
     ck.tight(ops.mm_nt(a, w, bias=bias, aux=aux, epilogue=ops.EPI_GELU), gelu64(vb), "gelu", rtol=3 * U)
     ck.tight(aux, vb, "gelu saved pre-activation", rtol=ONE)
-    if M >= 12000:     # wave-specialised kernel: C = gelu(saved z) exactly -- forward and backward meet at the same z
+    from focus_amd import _lib
+    route = _lib.lib().focus_gemm_last_kernel()                      # enum focus_gemm_kernel of the GELU launch above
+    ck.rows.append("%-52s %d" % ("kernel family (2 = NT_WS, 4 = NT_SMALL, 1 = NT)", route))
+    if not any(k in os.environ for k in GEMM_SWITCHES):
+        # a dispatch change must not move the bench shapes (or the recurrent Linears) onto another kernel unnoticed
+        if shape in BENCH_SHAPES:
+            assert route == 2, "bench shape %s left the wave-specialised kernel (family %d)" % (shape, route)
+        if shape in SMALL_SHAPES:
+            assert route == 4, "small shape %s left gemm_mfma_small (family %d)" % (shape, route)
+    if route == 2:     # wave-specialised kernel: C = gelu(saved z) exactly -- forward and backward meet at the same z
         ck.tight(ops.mm_nt(a, w, bias=bias, aux=aux, epilogue=ops.EPI_GELU), gelu64(aux.double()),
                  "gelu of the saved pre-activation", rtol=ONE)
     ck.tight(ops.mm_nt(a, w, bias=bias, epilogue=ops.EPI_RELU, residual=res), torch.relu(vb) + res.double(),
@@ -111,13 +125,13 @@ def test_nt_gemm_epilogues(shape):
     if not big:
         ck.tight(ops.mm_nt(a, w, bias=bias, epilogue=ops.EPI_TANH), torch.tanh(vb), "tanh", rtol=TWO)
     # backward forms: C = round(z) * act'(aux)
-    from focus_amd import _lib
     x = aux_in.double()
     ck.tight(ops.mm_nt(a, w, aux=aux_in, epilogue=_lib.EPI_DGELU), v0 * dgelu64(x), "dgelu", rtol=TWO)
     if not big:
         ck.tight(ops.mm_nt(a, w, aux=aux_in, epilogue=_lib.EPI_DRELU), v0 * (x > 0), "drelu", rtol=ONE)
         ck.tight(ops.mm_nt(a, w, aux=aux_in, epilogue=_lib.EPI_DTANH), v0 * (1 - x * x), "dtanh", rtol=TWO)
-        # fp32 output of the same kernel family (split-K path): no output rounding, fp32 accumulation order only
+        # fp32 output of the same kernel family, direct epilogue: no output rounding, fp32 accumulation order only.
+        # (Not split-K: that needs accumulate=1, which mm_nt never sets; tests/test_gpu_gemm_desc.py reaches it.)
         ck.tight(ops.mm_nt(a, w, out_dtype=torch.float32), v0, "fp32 out", rtol=1e-4)
     ck.done()
 
