@@ -1727,6 +1727,140 @@ def small_attention(q, k, v, heads, scale, causal=False, drop=None):
 
 
 # --------------------------------------------------------------------------------------------------
+# Greedy generation (STEVE.decode, steve.py:359-381): one query row against a key/value cache, and the arg-max /
+# embedding that ends a step (csrc/decode_attn.hip).  Inference only: no autograd nodes.
+# --------------------------------------------------------------------------------------------------
+def _no_grad_inputs(what, *ts):
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts):
+        raise RuntimeError("focus_amd: %s is inference only (no backward); call it under torch.no_grad() or detach its "
+                           "inputs" % what)
+
+
+def decode_attention_ok(max_len, d_model, heads, dtype):
+    """True when ops.decode_attention takes caches of max_len rows of d_model = heads * d channels in `dtype`."""
+    if dtype not in (torch.float32, torch.bfloat16) or heads < 1 or d_model % heads:
+        return False
+    return bool(_lib.lib().focus_decode_attn_ok(int(max_len), d_model // heads, BF16 if dtype == torch.bfloat16 else F32))
+
+
+def _rows2(t, what):
+    """[B, C] or [B, 1, C] with unit channel stride -> (the [B, C] view, its row stride)."""
+    if t.dim() == 3:
+        assert t.shape[1] == 1, "%s: one row per sequence" % what
+        t = t[:, 0]
+    assert t.dim() == 2 and t.stride(1) == 1, "%s: [B, C] rows with unit channel stride" % what
+    return t, t.stride(0)
+
+
+class Prepared:
+    """Launches whose arguments do not change from one generation step to the next -- the Linear products and LayerNorms
+    of a decoder block on fixed buffers -- built once and replayed with one ctypes call each.  At a few hundred rows the
+    step is bound by the host: through the autograd operators above a launch costs ~20 us of Python, here ~2 us.
+    Inference only; the launches go to the stream that was current when the object was made."""
+
+    def __init__(self):
+        self.calls, self.keep = [], []
+        self.stream = torch.cuda.current_stream().cuda_stream
+
+    def linear(self, x, w, out, bias=None, residual=None, epilogue=EPI_NONE):
+        """out [M, N] = epi(x [M, K] . w^T + bias) + residual; w: an [N, K] operand in x's dtype (ops.shadow)."""
+        M, K = x.shape
+        N = w.shape[0]
+        assert w.shape[1] == K and out.shape == (M, N) and x.dtype == w.dtype == out.dtype
+        assert x.stride(1) == 1 and w.stride(1) == 1 and out.is_contiguous() and out is not residual
+        assert residual is None or (residual.shape == out.shape and residual.is_contiguous() and residual.dtype == out.dtype)
+        d = GemmDesc()
+        d.M, d.N, d.K, d.batch0, d.batch1 = M, N, K, 1, 1
+        d.A, d.rsA, d.csA = x.data_ptr(), x.stride(0), 1
+        d.B, d.rsB, d.csB = w.data_ptr(), 1, w.stride(0)
+        d.C, d.rsC, d.csC = out.data_ptr(), N, 1
+        d.bias = bias.data_ptr() if bias is not None else None
+        d.residual = residual.data_ptr() if residual is not None else None
+        d.alpha, d.epilogue, d.dtype_ab, d.dtype_c = 1.0, epilogue, _dt(x), _dt(out)
+        self.keep.append((d, x, w, out, bias, residual))
+        self.calls.append((_lib.lib().focus_gemm, (ctypes.byref(d), ctypes.c_void_p(self.stream)), "gemm"))
+
+    def layer_norm(self, x, gamma, beta, eps, out):
+        rows, D = x.shape
+        assert x.is_contiguous() and out.is_contiguous() and out.shape == x.shape and out.dtype == x.dtype
+        stats = torch.empty(2, rows, device=x.device, dtype=torch.float32)
+        self.keep.append((x, gamma, beta, out, stats))
+        self.calls.append((_lib.lib().focus_layernorm_fwd, (_p(x), _p(gamma), _p(beta), _p(out), _p(stats[0]), _p(stats[1]),
+                                                            rows, D, eps, _dt(x), ctypes.c_void_p(self.stream)), "layernorm_fwd"))
+
+    def run(self):
+        for fn, args, what in self.calls:
+            status = fn(*args)
+            if status:
+                _lib.check(status, what)
+
+
+def layer_norm_into(x, gamma, beta, eps, out, stats):
+    """out = LayerNorm(x) for dense [rows, D] x and out, no autograd node; stats: [2, rows] fp32 scratch (mean, rstd)."""
+    _need_gpu(x, out)
+    rows, D = x.shape
+    assert x.is_contiguous() and out.is_contiguous() and out.shape == x.shape and out.dtype == x.dtype
+    assert stats.shape == (2, rows) and stats.dtype == torch.float32 and stats.is_contiguous()
+    _lib.check(_lib.lib().focus_layernorm_fwd(_p(x), _p(gamma), _p(beta), _p(out), _p(stats[0]), _p(stats[1]), rows, D, eps,
+                                              _dt(x), _stream()), "layernorm_fwd")
+    return out
+
+
+def stacked_weights(ws, dtype):
+    """The rows of several [C, Cin] weights in `dtype` as one [sum C, Cin] operand (what ops.linear_qkv multiplies by)."""
+    return _stacked_cat(tuple(ws), dtype, False)
+
+
+def decode_attention(q, k_new, v_new, k_cache, v_cache, len, heads, scale, out=None):
+    """softmax(scale q K^T) V per head for ONE query row per sequence over rows 0 .. len-1 of the caches [B, Lmax, C].
+    q [B, C] (or [B, 1, C]); with k_new / v_new (same shape; the three may be the column blocks of one ops.linear_qkv
+    output) row len-1 of the caches is written from them first; with both None the caches are only read.  -> [B, C]
+    (shaped like q; `out`: a dense buffer of that shape to write instead of a new tensor)."""
+    _no_grad_inputs("decode_attention", q, k_new, v_new, k_cache, v_cache)
+    _need_gpu(q, k_new, v_new, k_cache, v_cache)
+    assert (k_new is None) == (v_new is None), "k_new and v_new come together"
+    q2, ldq = _rows2(q, "q")
+    B, C = q2.shape
+    ldn = 0
+    if k_new is not None:
+        k_new, ldn = _rows2(k_new, "k_new")
+        v_new, ldv = _rows2(v_new, "v_new")
+        assert ldv == ldn and k_new.shape == v_new.shape == q2.shape, "k_new and v_new: rows like q's, one stride"
+    assert k_cache.shape == v_cache.shape and k_cache.dim() == 3 and k_cache.shape[0] == B and k_cache.shape[2] == C
+    assert k_cache.stride() == v_cache.stride() and k_cache.stride(2) == 1
+    assert k_cache.dtype == v_cache.dtype == q.dtype and (k_new is None or k_new.dtype == v_new.dtype == q.dtype)
+    if out is None:
+        out = torch.empty(q.shape, device=q.device, dtype=q.dtype)
+    else:
+        assert out.shape == q.shape and out.dtype == q.dtype and out.is_contiguous() and out.is_cuda
+    _lib.check(_lib.lib().focus_decode_attn(_p(q2), ldq, _p(k_new), _p(v_new), ldn, _p(k_cache), _p(v_cache), k_cache.stride(1),
+                                            k_cache.stride(0), _p(out), C, B, heads, C // heads, int(len), k_cache.shape[1],
+                                            float(scale), _dt(q), _stream()), "decode_attn")
+    return out
+
+
+def greedy_next(logits, dictionary, pe_row, out_tok=None):
+    """The end of a generation step: out_tok[b] = argmax(logits[b]) (int64, lowest index on ties; out_tok may be a column
+    of the [B, gen_len] token table) and the next input row dictionary[token] + pe_row in the dtype of the logits.
+    logits [B, V]; dictionary [V, D] and pe_row [D] fp32.  -> x_next [B, D]; the tokens are in out_tok."""
+    _no_grad_inputs("greedy_next", logits, dictionary, pe_row)
+    _need_gpu(logits, dictionary, pe_row, out_tok)
+    logits, ldl = _rows2(logits, "logits")
+    B, V = logits.shape
+    D = dictionary.shape[1]
+    assert dictionary.dtype == torch.float32 and pe_row.dtype == torch.float32 and dictionary.is_contiguous()
+    assert dictionary.shape[0] == V and pe_row.shape == (D,) and pe_row.is_contiguous()
+    if out_tok is None:
+        out_tok = torch.empty(B, device=logits.device, dtype=torch.long)
+    assert out_tok.dtype == torch.long and out_tok.shape == (B,) and (B == 1 or out_tok.stride(0) >= 1)
+    x = torch.empty(B, D, device=logits.device, dtype=logits.dtype)
+    _lib.check(_lib.lib().focus_greedy_next(_p(logits), ldl, _p(dictionary), _p(pe_row), _p(out_tok),
+                                            out_tok.stride(0) if B > 1 else 1, _p(x), D, B, V, D, _dt(logits), _stream()),
+               "greedy_next")
+    return x
+
+
+# --------------------------------------------------------------------------------------------------
 # RoIAlign, per-RoI max, box layout
 # --------------------------------------------------------------------------------------------------
 class _RoiAlignFn(torch.autograd.Function):

@@ -352,6 +352,8 @@ class STEVE(nn.Module):
         self.conv_dtype = torch.bfloat16 if (self.compute_dtype == torch.bfloat16 and
                                              os.environ.get("FOCUS_STEVE_CONV_BF16", "1") != "0") else None
         self.fused_rows = os.environ.get("FOCUS_STEVE_ROWS", "1") != "0"
+        # FOCUS_STEVE_DECODE_CACHE=0: decode() re-runs the decoder over the whole prefix for every token (the reference's loop)
+        self.decode_cache = os.environ.get("FOCUS_STEVE_DECODE_CACHE", "1") != "0"
         if self.channels_last:
             self.dvae.to(memory_format=torch.channels_last)
             self.steve_encoder.cnn.to(memory_format=torch.channels_last)
@@ -471,21 +473,46 @@ class STEVE(nn.Module):
         return slots, attns_vis, attns
 
     def decode(self, slots):
-        """steve.py:359-381: greedy autoregressive token generation, then the dVAE decoder."""
+        """steve.py:359-381: greedy autoregressive token generation, then the dVAE decoder.  In eval mode on the GPU the
+        tokens come from _generate_cached (one decoder step per token); otherwise, and with FOCUS_STEVE_DECODE_CACHE=0, from
+        the reference's loop over the growing prefix."""
         B, num_slots, slot_size = slots.size()
         H_enc, W_enc = self.image_size // 4, self.image_size // 4
         gen_len = H_enc * W_enc
         dec = self.steve_decoder
         slots = ops.linear(slots.to(self.compute_dtype), self.steve_encoder.slot_proj.weight)
-        z_gen = slots.new_zeros(0, dtype=torch.long)
-        input = dec.bos.expand(B, 1, -1)
-        for _ in range(gen_len):
-            decoder_output = dec.tf(dec.pos(input).to(self.compute_dtype), slots)
-            z_next = ops.linear(decoder_output[:, -1:].contiguous(), dec.head.weight).argmax(dim=-1)      # B, 1
-            z_gen = torch.cat((z_gen, z_next), dim=1)
-            input = torch.cat((input, dec.dict.dictionary(z_next)), dim=1)
+        heads = dec.tf.blocks[0].self_attn.num_heads if len(dec.tf.blocks) else 1
+        if (self.decode_cache and not self.training and slots.is_cuda
+                and ops.decode_attention_ok(gen_len, self.d_model, heads, self.compute_dtype)):
+            z_gen = self._generate_cached(slots, gen_len)
+        else:
+            z_gen = slots.new_zeros(0, dtype=torch.long)
+            input = dec.bos.expand(B, 1, -1)
+            for _ in range(gen_len):
+                decoder_output = dec.tf(dec.pos(input).to(self.compute_dtype), slots)
+                z_next = ops.linear(decoder_output[:, -1:].contiguous(), dec.head.weight).argmax(dim=-1)      # B, 1
+                z_gen = torch.cat((z_gen, z_next), dim=1)
+                input = torch.cat((input, dec.dict.dictionary(z_next)), dim=1)
         z_gen = F.one_hot(z_gen, self.vocab_size).transpose(1, 2).float().reshape(B, -1, H_enc, W_enc)
         return self.dvae.decoder(z_gen).clamp(0.0, 1.0)
+
+    @torch.no_grad()
+    def _generate_cached(self, slots, gen_len):
+        """The token loop of decode() with the decoder's keys and values cached: one TransformerDecoder.step per token
+        instead of a pass over the whole prefix.  slots [B, K, d_model] (projected) -> token ids [B, gen_len]."""
+        dec = self.steve_decoder
+        B = slots.shape[0]
+        cache = dec.tf.init_cache(slots, gen_len)
+        z_gen = torch.empty(B, gen_len, device=slots.device, dtype=torch.long)
+        pe = dec.pos.pe[0]                                                                # 1 + gen_len rows, fp32
+        x = (dec.bos[0] + pe[:1]).to(self.compute_dtype).expand(B, -1).contiguous()      # B, d_model: BOS at position 0
+        table = dec.dict.dictionary.weight
+        for t in range(gen_len):
+            h = dec.tf.step(x.unsqueeze(1), cache, t)                                     # B, 1, d_model
+            logits = ops.linear(h[:, 0], dec.head.weight)                                 # B, vocab
+            # arg-max token into column t, and the next input row dictionary[token] + pe[t + 1] in the compute type
+            x = ops.greedy_next(logits, table, pe[t + 1], z_gen[:, t])
+        return z_gen
 
     def reconstruct_autoregressive(self, video):
         """steve.py:383-392."""

@@ -1,7 +1,8 @@
 """Pre-LN transformer encoder (slot predictor) and decoder (autoregressive token decoder) of STEVE (mirror of
 slowfast/models/STEVE/transformer.py:4-193).  Attention runs as strided batched GEMMs + a row softmax through the C
 ABI (ops.small_attention: plain, causal, or cross-attention over the slots); Linear / LayerNorm / FFN are the fused HIP
-ops of the hot path."""
+ops of the hot path.  TransformerDecoder.init_cache / step generate one token at a time against cached keys and values
+(ops.decode_attention, csrc/decode_attn.hip): the evaluation path of STEVE.decode."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -162,3 +163,88 @@ class TransformerDecoder(_BlockStack):
     def __init__(self, num_blocks, max_len, d_model, num_heads, dropout=0.0):
         super().__init__(num_blocks, d_model, 3, lambda gain, first: TransformerDecoderBlock(
             max_len, d_model, num_heads, dropout, gain, is_first=first))
+
+    # ---- generation: one token per call against cached keys and values (STEVE.decode) ----
+    def init_cache(self, encoder_output, max_len):
+        """The state of `step` for encoder_output [B, S, D] and up to max_len generated positions: a list with one
+        (self_k, self_v, cross_k, cross_v) per block -- the zero-initialised self-attention caches [B, max_len, D] that
+        `step` fills row by row, and the keys / values of the slots, projected once -- which also carries the step's
+        buffers and its launches with fixed arguments (ops.Prepared), built here once."""
+        B, _, D = encoder_output.shape
+        dt, dev = encoder_output.dtype, encoder_output.device
+        own = encoder_output.new_zeros(len(self.blocks), 2, B, max_len, D)
+        cache = _DecoderCache()
+        new = lambda n: torch.empty(B, n, device=dev, dtype=dt)
+        cache.res = (new(D), new(D))                     # the residual stream, written alternately (no in-place product)
+        y, qkv, q2, cache.att = new(D), new(3 * D), new(D), new(D)
+        cache.q, cache.k_new, cache.v_new, cache.q2 = qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], q2
+        cache.stats = torch.empty(2, B, device=dev, dtype=torch.float32)
+        cache.stream = torch.cuda.current_stream().cuda_stream      # the prepared launches are bound to it
+        cur = 0                                          # which of cache.res holds the residual stream
+        for i, block in enumerate(self.blocks):
+            sa, ca, ffn = block.self_attn, block.encoder_decoder_attn, block.ffn
+            ck, cv = ops.linear_kv(encoder_output, ca.proj_k.weight, ca.proj_v.weight)
+            cache.append((own[i, 0], own[i, 1], ck, cv))
+            w = lambda p: ops.shadow(p, dt)
+            hid = new(ffn[0].weight.shape[0])
+            pre, mid, post = ops.Prepared(), ops.Prepared(), ops.Prepared()
+            ln = block.self_attn_layer_norm
+            if i == 0:       # is_first: step() normalises its input into res[0], which is residual stream and branch input
+                assert block.is_first
+                pre.linear(cache.res[0], ops.stacked_weights((sa.proj_q.weight, sa.proj_k.weight, sa.proj_v.weight), dt), qkv)
+            else:
+                assert not block.is_first
+                pre.layer_norm(cache.res[cur], ln.weight, ln.bias, ln.eps, y)
+                pre.linear(y, ops.stacked_weights((sa.proj_q.weight, sa.proj_k.weight, sa.proj_v.weight), dt), qkv)
+            mid.linear(cache.att, w(sa.proj_o.weight), cache.res[cur ^ 1], residual=cache.res[cur])
+            cur ^= 1
+            ln = block.encoder_decoder_attn_layer_norm
+            mid.layer_norm(cache.res[cur], ln.weight, ln.bias, ln.eps, y)
+            mid.linear(y, w(ca.proj_q.weight), q2)
+            post.linear(cache.att, w(ca.proj_o.weight), cache.res[cur ^ 1], residual=cache.res[cur])
+            cur ^= 1
+            ln = block.ffn_layer_norm
+            post.layer_norm(cache.res[cur], ln.weight, ln.bias, ln.eps, y)
+            post.linear(y, w(ffn[0].weight), hid, bias=ffn[0].bias, epilogue=ops.EPI_RELU)
+            post.linear(hid, w(ffn[2].weight), cache.res[cur ^ 1], bias=ffn[2].bias, residual=cache.res[cur])
+            cur ^= 1
+            cache.launches.append((pre, mid, post))
+        cache.last = cur
+        return cache
+
+    def step(self, x_t, cache, t):
+        """x_t [B, 1, D]: the position-embedded input at index t -> the row forward() produces at index t, [B, 1, D].
+        Row t of every block's self-attention cache is written; calls must come in the order t = 0, 1, 2, ...
+        Per block: LN -> q | k | v in one product -> ops.decode_attention with append -> proj_o + residual -> LN -> proj_q
+        -> ops.decode_attention over the slots' cache -> proj_o + residual -> LN -> FFN + residual."""
+        assert not self.training, "TransformerDecoder.step is the evaluation path (the dropouts draw nothing here)"
+        assert not torch.is_grad_enabled() or not x_t.requires_grad, "TransformerDecoder.step is inference only"
+        B, D = cache.res[0].shape
+        assert x_t.shape == (B, 1, D) and x_t.dtype == cache.res[0].dtype
+        assert torch.cuda.current_stream().cuda_stream == cache.stream, "step() on another stream than init_cache()"
+        x2 = x_t.detach().reshape(B, D)
+        x2 = x2 if x2.is_contiguous() else x2.contiguous()
+        first = self.blocks[0].self_attn_layer_norm if len(self.blocks) else None
+        if first is not None:        # block 0 normalises the residual stream itself, as in forward()
+            ops.layer_norm_into(x2, first.weight, first.bias, first.eps, cache.res[0], cache.stats)
+        for block, (sk, sv, ck, cv), (pre, mid, post) in zip(self.blocks, cache, cache.launches):
+            heads = block.self_attn.num_heads
+            scale = (D // heads) ** -0.5
+            pre.run()
+            ops.decode_attention(cache.q, cache.k_new, cache.v_new, sk, sv, t + 1, heads, scale, out=cache.att)
+            mid.run()
+            ops.decode_attention(cache.q2, None, None, ck, cv, ck.shape[1], heads, scale, out=cache.att)
+            post.run()
+        src = cache.res[cache.last] if first is not None else x2
+        out = torch.empty(B, 1, D, device=src.device, dtype=src.dtype)
+        ops.layer_norm_into(src, self.layer_norm.weight, self.layer_norm.bias, self.layer_norm.eps, out.view(B, D), cache.stats)
+        return out
+
+
+class _DecoderCache(list):
+    """What TransformerDecoder.init_cache returns: the per-block (self_k, self_v, cross_k, cross_v), plus the buffers and
+    prepared launches of a step."""
+
+    def __init__(self):
+        super().__init__()
+        self.launches = []

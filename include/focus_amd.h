@@ -497,6 +497,26 @@ int focus_flash_attn_ok(int Nq, int Nk, int d, int dtype, int causal);
 int focus_flash_attn_fwd(const focus_flash_args* args, void* stream);
 int focus_flash_attn_bwd(const focus_flash_args* args, void* stream);
 
+/* One step of greedy autoregressive decoding (decode_attn.hip; steve.py:359-381, STEVE.decode): attention of ONE new query
+ * row per sequence over a key/value cache, and the arg-max / embedding that ends the step.
+ * focus_decode_attn: q, out [B, heads*d] rows ldq / ldo elements apart; k_cache, v_cache [B, Lmax, heads*d] with row stride
+ * ldc and batch stride bsc.  `len` (1 <= len <= Lmax) = number of valid keys AFTER the call.
+ *   k_new, v_new [B, heads*d] rows ldn apart (q | k_new | v_new may be the column blocks of one projection output): row
+ *   len-1 of both caches is first written from them bit for bit, then out = softmax(scale q K^T) V per head over rows
+ *   0 .. len-1.  Both NULL: the caches are only read (cross-attention over the projected slots, len = their number).
+ * Rows >= len of the caches are neither read into the result nor written; nothing else is written.
+ * d % 8 == 0, 8 <= d <= 64, fp32 or bf16 storage with fp32 accumulation (focus_decode_attn_ok).  Every pointer 16-byte
+ * aligned, every stride >= heads*d and a multiple of 16 bytes (FOCUS_ERR_ALIGN otherwise). */
+int focus_decode_attn_ok(int Lmax, int d, int dtype);
+int focus_decode_attn(const void* q, int64_t ldq, const void* k_new, const void* v_new, int64_t ldn, void* k_cache,
+                      void* v_cache, int64_t ldc, int64_t bsc, void* out, int64_t ldo, int B, int heads, int d, int len,
+                      int Lmax, float scale, int dtype, void* stream);
+/* tok[b * tok_stride] = argmax_v logits[b, v] (lowest index on ties; a NaN counts as the largest value, as in
+ * torch.argmax) and x_next[b, :] = dict[tok, :] + pe_row rounded to `dtype`: the next step's input row.  logits [B, V] and
+ * x_next [B, D] in `dtype` with row strides ldl / ldx; dict [V, D] and pe_row [D] fp32 dense. */
+int focus_greedy_next(const void* logits, int64_t ldl, const float* dict, const float* pe_row, int64_t* tok,
+                      int64_t tok_stride, void* x_next, int64_t ldx, int B, int V, int D, int dtype, void* stream);
+
 /* Both consumers of g = d(loss)/d(u) of the re-associated temporal step in one pass over g (traj_time2_gw.hip; autograd of
  * attention.py:536-549): dq2[r, h*d+dd] = sum_c g[h,r,c] Wk[h*d+dd, c] and dWk[h*d+dd, c] = sum_r q2[r, h*d+dd] g[h,r,c].
  * g [heads][R][C] bf16, q2 / dq2 [R][C] bf16, wk = the bf16 rows of Wk (row stride wk_ld), dwk [C][C] fp32 dense.
