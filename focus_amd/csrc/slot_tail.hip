@@ -1041,8 +1041,9 @@ extern "C" int focus_slot_tail_fwd(const focus_slot_tail_args* args, void* strea
     const focus_slot_tail_args& a = *args;
     if (a.R <= 0) return FOCUS_OK;
     if (!focus_slot_tail_ok(a.D, a.H, FOCUS_BF16)) return FOCUS_ERR_SHAPE;
+    if (a.do_mlp && !a.do_gru) return FOCUS_ERR_SHAPE;               // the MLP normalises h' and adds to it: no such chain
     if (!a.h || (a.do_gru && (!a.upd || !a.w_ih || !a.w_hh || !a.b_ih || !a.b_hh || !a.g || !a.hn))) return FOCUS_ERR_NULL;
-    if (a.do_mlp && (!a.do_gru || !a.ln1_g || !a.ln1_b || !a.w1 || !a.b1 || !a.w2 || !a.b2 || !a.y || !a.mean1 || !a.rstd1 || !a.a || !a.s))
+    if (a.do_mlp && (!a.ln1_g || !a.ln1_b || !a.w1 || !a.b1 || !a.w2 || !a.b2 || !a.y || !a.mean1 || !a.rstd1 || !a.a || !a.s))
         return FOCUS_ERR_NULL;
     if (a.do_q && (!a.ln2_g || !a.ln2_b || !a.wq || !a.sn || !a.mean2 || !a.rstd2 || !a.q)) return FOCUS_ERR_NULL;
     // the right-sized launches by default (STEVE slot update, whole-step graph: 17.5 -> 16.2 ms; graphed product loop 20.5 ->
@@ -1057,12 +1058,17 @@ extern "C" int focus_slot_tail_bwd_blocks(int R) { return (R + ROWS - 1) / ROWS;
 
 extern "C" int focus_slot_tail_bwd(const focus_slot_tail_bwd_args* args, void* stream) {
     if (!args) return FOCUS_ERR_NULL;
-    const focus_slot_tail_bwd_args& a = *args;
+    focus_slot_tail_bwd_args a = *args;
     if (a.R <= 0) return FOCUS_OK;
     if (!focus_slot_tail_ok(a.D, a.H, FOCUS_BF16)) return FOCUS_ERR_SHAPE;
+    if (a.do_mlp && !a.do_gru) return FOCUS_ERR_SHAPE;
     if (!a.dh) return FOCUS_ERR_NULL;
+    // ds is an output of the q and MLP stages only.  With neither, a caller's ds buffer is not this call's: the staged gate
+    // kernel would read the gradient arriving at h' from it (never written) instead of from dout, the one launch would copy
+    // dout into it.
+    if (!a.do_q && !a.do_mlp) a.ds = nullptr;
     if (a.do_q && (!a.dq || !a.cur || !a.mean2 || !a.rstd2 || !a.ln2_g || !a.wq_t || !a.ds || !a.part2)) return FOCUS_ERR_NULL;
-    if (a.do_mlp && (!a.do_gru || !a.a || !a.hn || !a.mean1 || !a.rstd1 || !a.ln1_g || !a.w1_t || !a.w2_t || !a.ds || !a.dz || !a.part1))
+    if (a.do_mlp && (!a.a || !a.hn || !a.mean1 || !a.rstd1 || !a.ln1_g || !a.w1_t || !a.w2_t || !a.ds || !a.dz || !a.part1))
         return FOCUS_ERR_NULL;
     if (a.do_gru && (!a.g || !a.h || !a.w_ih_t || !a.w_hh_t || !a.dg || !a.dupd)) return FOCUS_ERR_NULL;
     const char* env = getenv("FOCUS_SLOT_TAIL_STAGED");             // 1 (default): five right-sized launches; 0: one launch

@@ -440,7 +440,14 @@ int focus_linear_wgrad_group(const focus_wgrad_item* items, int n_items, const v
  * is s, hn or (do_gru == 0: "q only") the input h itself.  R rows of D (= 192) channels, hidden width H (= 768); bf16
  * activations and weights ([out, in] row-major, the bf16 working copies), fp32 biases / LayerNorm parameters / statistics.
  * Every intermediate a backward needs is an output: g [2,R,3D] (gate pre-activations incl. bias), hn, y = LN1(hn) with
- * mean1 / rstd1 [R], a = relu(..) [R,H], s, sn = LN2(slots) with mean2 / rstd2, q. */
+ * mean1 / rstd1 [R], a = relu(..) [R,H], s, sn = LN2(slots) with mean2 / rstd2, q.
+ * Status (pinned by tests/test_gpu_slot_tail.py; a refused call writes nothing): args NULL is FOCUS_ERR_NULL; R <= 0 returns
+ * FOCUS_OK without a launch, whatever else the arguments hold; D, H other than 192, 768 and do_mlp without do_gru (the MLP
+ * normalises h' and adds to it) are FOCUS_ERR_SHAPE; a NULL pointer of a stage that is switched on (h always) is
+ * FOCUS_ERR_NULL.  The pointers of a stage that is switched off are not looked at and its outputs are not written.  Rows are
+ * dense (stride D, H, 3D; plane 1 of g starts at row R); nothing is read or written past row R - 1 of any tensor.
+ * FOCUS_SLOT_TAIL_STAGED (read per call; default 1) selects four right-sized launches (1) or one launch (0): same stored
+ * values, LayerNorm sums associated differently. */
 typedef struct focus_slot_tail_args {
     int32_t R, D, H, do_gru, do_mlp, do_q;
     float ln1_eps, ln2_eps;
@@ -458,7 +465,17 @@ int focus_slot_tail_fwd(const focus_slot_tail_args* args, void* stream);
  * tensors (cur = the slots LayerNorm_slots normalised: s, or hn without the MLP, or h without the GRU).  Outputs: dupd, dh
  * [R,D]; the dY rows the weight gradients are later formed from: ds [R,D] (fc2; also with do_q alone), dz [R,H] (fc1), dg
  * [2,R,3D] (W_ih, W_hh) (dq itself is Wq's); LayerNorm parameter partials part1 / part2 [2][focus_slot_tail_bwd_blocks(R)][D]
- * fp32 ([0] = d gamma, [1] = d beta; sum over the blocks). */
+ * fp32 ([0] = d gamma, [1] = d beta; sum over the blocks; a block is 16 consecutive rows).
+ * Which outputs a call writes: dh always; dupd, dg with do_gru; dz, part1, ds with do_mlp (without do_q: ds = dout, zeros for
+ * NULL); part2, ds with do_q -- except the staged form without do_gru, which writes dh only (dh = ds there; the one launch
+ * writes both); with neither do_q nor do_mlp ds is not looked at.  Everything else keeps its contents.
+ * Status (pinned by tests/test_gpu_slot_tail.py; a refused call writes nothing): args NULL is FOCUS_ERR_NULL; R <= 0 returns
+ * FOCUS_OK without a launch; D, H other than 192, 768 and do_mlp without do_gru are FOCUS_ERR_SHAPE; dh NULL, or a NULL input
+ * or output of a stage that is switched on, is FOCUS_ERR_NULL (do_q: dq, cur, mean2, rstd2, ln2_g, wq_t, ds, part2; do_mlp: a,
+ * hn, mean1, rstd1, ln1_g, w1_t, w2_t, ds, dz, part1; do_gru: g, h, w_ih_t, w_hh_t, dg, dupd).  The staged form
+ * (FOCUS_SLOT_TAIL_STAGED unset or non-zero) further needs its scratch, ws_dsn with do_q, ws_dy1 with do_mlp, ws_res with
+ * do_gru (FOCUS_ERR_WORKSPACE), and has nothing to launch with neither do_gru nor do_q (FOCUS_ERR_SHAPE; the one launch
+ * copies dout to dh). */
 typedef struct focus_slot_tail_bwd_args {
     int32_t R, D, H, do_gru, do_mlp, do_q;
     const void* dout; const void* dq;
