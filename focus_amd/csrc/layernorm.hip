@@ -378,6 +378,8 @@ inline bool ln_v16_ok(const void* a, const void* b, const void* c, const void* d
         else CALL(64, 2);                                            \
     } while (0)
 
+inline size_t ln_vec_bytes(int dtype) { return dtype == FOCUS_BF16 ? 8 : 16; }
+
 template <typename T>
 int ln_fwd_launch(const void* x, const float* g, const float* b, void* y, float* mean, float* rstd, int rows, int D,
                   float eps, int rpb, int64_t xbs, hipStream_t s) {
@@ -408,10 +410,12 @@ int ln_bwd_launch(const void* dy, const void* x, const float* g, const float* me
 
 static int ln_fwd_any(const void* x, int rpb, int64_t xbs, const float* gamma, const float* beta, void* y, float* mean,
                       float* rstd, int rows, int D, float eps, int dtype, void* stream) {
-    if (!x || !gamma || !beta || !y || !mean || !rstd) return FOCUS_ERR_NULL;
+    // (an empty tensor has no address: with rows == 0 the row-sized buffers may be NULL)
+    if (!gamma || !beta || (rows > 0 && (!x || !y || !mean || !rstd))) return FOCUS_ERR_NULL;
     if (rows <= 0) return FOCUS_OK;
     if (D <= 0 || (D & 3) || D > MAXV * 256 || rpb <= 0 || (xbs & 3)) return FOCUS_ERR_SHAPE;
-    if (!focus_aligned(x, 8) || !focus_aligned(y, 8) || !focus_aligned(gamma, 16) || !focus_aligned(beta, 16))
+    const size_t va = ln_vec_bytes(dtype);                         // ld4 / st4: 4 elements = 8 bytes bf16, 16 bytes fp32
+    if (!focus_aligned(x, va) || !focus_aligned(y, va) || !focus_aligned(gamma, 16) || !focus_aligned(beta, 16))
         return FOCUS_ERR_ALIGN;
     hipStream_t s = (hipStream_t)stream;
     if (ln_v16_ok(x, y, gamma, beta, rows, D, xbs, dtype)) {
@@ -447,11 +451,23 @@ extern "C" int focus_layernorm_bwd_blocks(int rows) {
 static int ln_bwd_any(const void* dy, const void* x, int rpb, int64_t xbs, const float* gamma, const float* mean,
                       const float* rstd, const void* dres, void* dx, float* dgamma, float* dbeta, float* partial, int rows,
                       int D, int dtype, void* stream) {
-    if (!dy || !x || !gamma || !mean || !rstd || !dx || !partial) return FOCUS_ERR_NULL;
+    // (an empty tensor has no address: with rows == 0 the row-sized buffers may be NULL)
+    if (!gamma || !partial || (rows > 0 && (!dy || !x || !mean || !rstd || !dx))) return FOCUS_ERR_NULL;
     if (!dgamma != !dbeta) return FOCUS_ERR_NULL;                   // both, or neither: the caller sums `partial` itself
     const bool finish = dgamma != nullptr;
-    if (D <= 0 || (D & 3) || D > MAXV * 256 || rows <= 0 || rpb <= 0 || (xbs & 3)) return FOCUS_ERR_SHAPE;
+    if (D <= 0 || (D & 3) || D > MAXV * 256 || rows < 0 || rpb <= 0 || (xbs & 3)) return FOCUS_ERR_SHAPE;
+    const size_t va = ln_vec_bytes(dtype);                         // ld4 / st4: 4 elements = 8 bytes bf16, 16 bytes fp32
+    if (!focus_aligned(dy, va) || !focus_aligned(x, va) || !focus_aligned(dx, va) || (dres && !focus_aligned(dres, va)) ||
+        !focus_aligned(gamma, 16))
+        return FOCUS_ERR_ALIGN;
     hipStream_t s = (hipStream_t)stream;
+    if (rows == 0) {                                                // no rows: zero gradients, partial[2][1][D] of zeros
+        if (hipMemsetAsync(partial, 0, (size_t)2 * D * sizeof(float), s) != hipSuccess) return FOCUS_ERR_LAUNCH;
+        if (finish && (hipMemsetAsync(dgamma, 0, (size_t)D * sizeof(float), s) != hipSuccess ||
+                       hipMemsetAsync(dbeta, 0, (size_t)D * sizeof(float), s) != hipSuccess))
+            return FOCUS_ERR_LAUNCH;
+        return FOCUS_OK;
+    }
     const int nblk = focus_layernorm_bwd_blocks(rows);
     if (ln_v16_ok(dy, x, dx, dres, rows, D, xbs, dtype) && focus_aligned(gamma, 16)) {
     // nblk is capped (the finish walks nblk partial rows): beyond 64 rows per wave the workgroups get 8 waves instead of 4,

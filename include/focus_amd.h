@@ -155,7 +155,18 @@ int focus_layernorm_fwd(const void* x, const float* gamma, const float* beta, vo
  * pre-norm block (x -> x + f(LN(x)), attention.py:116-126); it is added into dx in the same pass, replacing the
  * separate accumulation autograd would do.  dgamma == dbeta == NULL: only `partial` is written -- partial[0] holds nblk row
  * vectors whose sum is dgamma, partial[1] likewise dbeta -- for a caller that applies the same LayerNorm many times and
- * reduces all applications' partials in one pass at the end (STEVE's slot loop: 213 applications per step). */
+ * reduces all applications' partials in one pass at the end (STEVE's slot loop: 213 applications per step).
+ *
+ * Statuses of the four entry points below, judged in this order before any launch; a refused call writes nothing
+ * (pinned by tests/test_ln_ref_cpu.py and tests/test_gpu_layernorm.py):
+ *   FOCUS_ERR_NULL   gamma, beta (forward) or partial (backward) is NULL; a row-sized buffer (x, y, mean, rstd, dy, dx) is
+ *                    NULL while rows > 0; dgamma without dbeta or the reverse.
+ *   FOCUS_ERR_SHAPE  D <= 0, D % 4 != 0, D > 4096, rows_per_block <= 0, block_stride % 4 != 0, rows < 0 (backward).
+ *   FOCUS_ERR_ALIGN  x, y, dy, dx or a non-NULL dres not aligned to 4 elements of `dtype` (16 bytes fp32, 8 bytes bf16), or
+ *                    gamma / beta not to 16 bytes.
+ *   FOCUS_OK         rows == 0 included: the forward does nothing (rows <= 0, before the shape is judged); the backward
+ *                    zero-fills dgamma and dbeta when given and partial[2][1][D] (focus_layernorm_bwd_blocks(0) == 1) on
+ *                    the stream.  With rows == 0 the row-sized buffers may be NULL: an empty tensor has no address. */
 int focus_layernorm_bwd_blocks(int rows);
 int focus_layernorm_bwd(const void* dy, const void* x, const float* gamma, const float* mean,
                         const float* rstd, const void* dres, void* dx, float* dgamma, float* dbeta, float* partial,
