@@ -2783,3 +2783,117 @@ _SLOT_TAIL_BWD = _os.environ.get("FOCUS_SLOT_TAIL_BWD", "0") != "0"
 def slot_tail(upd, h, params, gru=True, mlp=True, q=True):
     """-> (slots [R,D], q [R,D] or None).  upd, h [R,D] bf16 (upd is ignored without gru); see the section comment."""
     return _SlotTailFn.apply(upd, h, float(params.eps[0]), float(params.eps[1]), bool(gru), bool(mlp), bool(q), *params.tensors)
+
+
+# --------------------------------------------------------------------------------------------------
+# BatchNorm2d and MaxPool2d(3, 2, 1) over channels-last feature maps (csrc/batchnorm.hip): the ResNet-18 trunk of STEVE
+# --------------------------------------------------------------------------------------------------
+def _nhwc_rows(x, dtype=None):
+    """[N,C,H,W] of any memory format -> its [N*H*W, C] row matrix, dense (a view of a channels-last tensor)."""
+    C = x.shape[1]
+    r = x.permute(0, 2, 3, 1).reshape(-1, C)
+    if dtype is not None and r.dtype != dtype:
+        r = r.to(dtype)
+    return r.contiguous()
+
+
+def _nchw_view(rows, N, H, W):
+    """The [N*H*W, C] row matrix as a channels-last [N,C,H,W] tensor."""
+    return rows.view(N, H, W, rows.shape[1]).permute(0, 3, 1, 2)
+
+
+def _bn_workspace(L, R, C, device):
+    return torch.empty(L.focus_bn_workspace_bytes(R, C), device=device, dtype=torch.uint8)
+
+
+class _BatchNormFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, residual, running_mean, running_var, training, momentum, eps, relu):
+        N, C, H, W = x.shape
+        x2 = _nhwc_rows(x)
+        R = x2.shape[0]
+        L = _lib.lib()
+        if training:
+            # batch statistics; the running buffers are updated in place by the kernel (no host synchronisation)
+            mean = torch.empty(C, device=x.device, dtype=torch.float32)
+            rstd = torch.empty(C, device=x.device, dtype=torch.float32)
+            _lib.check(L.focus_bn_stats(_p(x2), _p(mean), _p(rstd), _p(running_mean), _p(running_var),
+                                        _p(_bn_workspace(L, R, C, x.device)), R, C, eps, momentum, _dt(x2), _stream()),
+                       "bn_stats")
+        else:
+            mean, rstd = running_mean, torch.rsqrt(running_var + eps)
+        r2 = None if residual is None else _nhwc_rows(residual, x2.dtype)
+        y2 = torch.empty_like(x2)
+        _lib.check(L.focus_bn_apply(_p(x2), _p(mean), _p(rstd), _p(weight), _p(bias), _p(r2), _p(y2), R, C, int(relu),
+                                    _dt(x2), _stream()), "bn_apply")
+        ctx.save_for_backward(x2, y2 if relu else None, mean, rstd, weight)
+        ctx.cfg = (N, H, W, bool(relu), not training, None if residual is None else residual.dtype)
+        return _nchw_view(y2, N, H, W)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, y2, mean, rstd, weight = ctx.saved_tensors
+        N, H, W, relu, frozen, res_dtype = ctx.cfg
+        R, C = x2.shape
+        L = _lib.lib()
+        dy2 = _nhwc_rows(dy, x2.dtype)
+        dx2 = torch.empty_like(x2)
+        dres2 = torch.empty_like(x2) if res_dtype is not None else None
+        dg = torch.empty(C, device=x2.device, dtype=torch.float32)
+        db = torch.empty(C, device=x2.device, dtype=torch.float32)
+        _lib.check(L.focus_bn_bwd(_p(dy2), _p(x2), _p(y2), _p(mean), _p(rstd), _p(weight), _p(dx2), _p(dres2), _p(dg), _p(db),
+                                  _p(_bn_workspace(L, R, C, x2.device)), R, C, int(relu), int(frozen), _dt(x2), _stream()),
+                   "bn_bwd")
+        dres = None if dres2 is None else _nchw_view(dres2, N, H, W).to(res_dtype)
+        return _nchw_view(dx2, N, H, W), dg, db, dres, None, None, None, None, None, None
+
+
+def batch_norm(x, weight, bias, running_mean, running_var, training, momentum, eps, relu=False, residual=None):
+    """nn.BatchNorm2d on the HIP kernels: act(BN(x) [+ residual]) -> channels-last [N,C,H,W] in x's type (fp32 or bf16; the
+    parameters and statistics are fp32).  training: batch statistics, running_mean / running_var (None: not tracked) updated
+    in place with `momentum`; else the running buffers normalise.  C % 8 == 0, C <= 256."""
+    _need_gpu(x, weight, bias, residual, running_mean, running_var)
+    if x.dim() != 4:
+        raise RuntimeError("focus_amd: batch_norm takes [N,C,H,W] (got %d dimensions)" % x.dim())
+    if momentum is None:
+        raise RuntimeError("focus_amd: batch_norm with momentum=None (cumulative moving average) is not built")
+    if (running_mean is None) != (running_var is None) or (not training and running_mean is None):
+        raise RuntimeError("focus_amd: batch_norm needs both running buffers (or, in training mode, neither)")
+    for t in (weight, bias, running_mean, running_var):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise RuntimeError("focus_amd: batch_norm parameters and statistics are dense fp32 vectors")
+    return _BatchNormFn.apply(x, weight, bias, residual, running_mean, running_var, bool(training), float(momentum),
+                              float(eps), bool(relu))
+
+
+class _MaxPool3x3S2Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        N, C, H, W = x.shape
+        OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        x2 = _nhwc_rows(x)
+        y2 = torch.empty(N * OH * OW, C, device=x.device, dtype=x2.dtype)
+        idx = torch.empty(N * OH * OW, C, device=x.device, dtype=torch.int8)
+        _lib.check(_lib.lib().focus_maxpool_fwd(_p(x2), _p(y2), _p(idx), N, H, W, C, _dt(x2), _stream()), "maxpool_fwd")
+        ctx.save_for_backward(idx)
+        ctx.cfg = (N, H, W)
+        return _nchw_view(y2, N, OH, OW)
+
+    @staticmethod
+    def backward(ctx, dy):
+        idx, = ctx.saved_tensors
+        N, H, W = ctx.cfg
+        dy2 = _nhwc_rows(dy)
+        C = dy2.shape[1]
+        dx2 = torch.empty(N * H * W, C, device=dy.device, dtype=dy2.dtype)
+        _lib.check(_lib.lib().focus_maxpool_bwd(_p(dy2), _p(idx), _p(dx2), N, H, W, C, _dt(dy2), _stream()), "maxpool_bwd")
+        return _nchw_view(dx2, N, H, W)
+
+
+def max_pool_3x3_s2(x):
+    """nn.MaxPool2d(3, 2, 1) on [N,C,H,W] of any memory format -> channels-last; ties go to the first maximum of the window
+    in row-major order, as in ATen.  C % 8 == 0, C <= 256."""
+    _need_gpu(x)
+    if x.dim() != 4:
+        raise RuntimeError("focus_amd: max_pool_3x3_s2 takes [N,C,H,W] (got %d dimensions)" % x.dim())
+    return _MaxPool3x3S2Fn.apply(x)

@@ -3,6 +3,7 @@ slowfast/models/STEVE/steve.py).  The iterative slot update (SlotAttentionVideo,
 the HIP kernels; the model around it (STEVE.forward, :253-330 -- SURVEY.md section 8(f) rank 1) keeps the reference's
 module tree and state_dict keys: convolutions (dVAE, CNN encoder) and the Gumbel-softmax stay on ATen/MIOpen, every
 Linear / LayerNorm / FFN / attention of the encoder MLP, the slot projection and the decoder goes through the C ABI."""
+import contextlib
 import os
 
 import torch
@@ -258,23 +259,108 @@ class BaseCNN(nn.Module):
         return self.fenc(x)
 
 
+def _conv3x3(cin, cout, stride=1):
+    return nn.Conv2d(cin, cout, 3, stride, 1, bias=False)
+
+
+class BasicBlock(nn.Module):
+    """The two-convolution residual block of the public ResNet-18 structure (He et al. 2016), with its usual attribute names:
+    conv1, bn1, relu, conv2, bn2 and, where the shape changes, downsample = (1x1 convolution, BatchNorm)."""
+
+    def __init__(self, cin, cout, stride=1):
+        super().__init__()
+        self.conv1 = _conv3x3(cin, cout, stride)
+        self.bn1 = nn.BatchNorm2d(cout)
+        self.relu = nn.ReLU(inplace=True)
+        self.conv2 = _conv3x3(cout, cout)
+        self.bn2 = nn.BatchNorm2d(cout)
+        self.downsample = None
+        if stride != 1 or cin != cout:
+            self.downsample = nn.Sequential(nn.Conv2d(cin, cout, 1, stride, bias=False), nn.BatchNorm2d(cout))
+
+    def forward(self, x):
+        identity = x if self.downsample is None else self.downsample(x)
+        out = self.relu(self.bn1(self.conv1(x)))
+        return self.relu(self.bn2(self.conv2(out)) + identity)
+
+
+class ResNet18(nn.Module):
+    """Module tree, state_dict keys and initialisation of the stock ResNet-18: conv1 (7x7 / 2), bn1, relu, maxpool,
+    layer1..4 (two BasicBlocks each; 64, 128, 256, 512 channels), avgpool, fc.  Residual convolutions are initialised
+    kaiming_normal_(fan_out, relu), BatchNorm to weight 1 / bias 0, fc as nn.Linear does."""
+
+    def __init__(self, num_classes=1000):
+        super().__init__()
+        self.conv1 = nn.Conv2d(3, 64, 7, 2, 3, bias=False)
+        self.bn1 = nn.BatchNorm2d(64)
+        self.relu = nn.ReLU(inplace=True)
+        self.maxpool = nn.MaxPool2d(3, 2, 1)
+        cin = 64
+        for i, (cout, stride) in enumerate(((64, 1), (128, 2), (256, 2), (512, 2))):
+            setattr(self, "layer%d" % (i + 1), nn.Sequential(BasicBlock(cin, cout, stride), BasicBlock(cout, cout)))
+            cin = cout
+        self.avgpool = nn.AdaptiveAvgPool2d((1, 1))
+        self.fc = nn.Linear(512, num_classes)
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
+            elif isinstance(m, nn.BatchNorm2d):
+                nn.init.constant_(m.weight, 1)
+                nn.init.constant_(m.bias, 0)
+
+    def forward(self, x):
+        x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
+        x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
+        return self.fc(torch.flatten(self.avgpool(x), 1))
+
+
 class Res18Block(nn.Module):
-    """steve.py:176-203 (needs torchvision's resnet18, which this image does not ship: fails loudly when asked for)."""
+    """steve.py:176-203: a ResNet-18 whose conv1 is replaced by a 3x3 / 1 convolution WITH bias, run up to layer1 (fenc =
+    children()[:-5]: conv1, bn1, relu, maxpool, layer1), then ReLU and a stride-2 transposed convolution back to the image
+    size.  layer2..4, avgpool and fc are constructed and stay in the state_dict (reference checkpoints load strict) but never
+    run: their 47 parameters never receive a gradient.  fenc.* alias res18.* (the same Parameters under two names).
+
+    On the GPU the BatchNorms (training statistics, running buffers, affine, ReLU, residual sum) and the max-pool run on the
+    HIP kernels of csrc/batchnorm.hip (ops.batch_norm, ops.max_pool_3x3_s2); the convolutions stay on MIOpen.
+    FOCUS_STEVE_BN=0 (read at construction) selects F.batch_norm / F.max_pool2d over the same modules: the A/B switch, and
+    the only path that runs on the CPU."""
 
     def __init__(self, args):
         super().__init__()
-        try:
-            from torchvision.models import resnet18
-        except ImportError as e:
-            raise NotImplementedError("MODEL.CNN_NAME='res18' needs torchvision (steve.py:179)") from e
-        self.res18 = resnet18()
+        if args.SLOTS.CNN_HID_SIZE != 64 or args.SLOTS.IMG_SIZE != 64:
+            raise ValueError(
+                "MODEL.CNN_NAME='res18' needs SLOTS.CNN_HID_SIZE == 64 and SLOTS.IMG_SIZE == 64 (got %s, %s): the replaced "
+                "conv1 feeds the stock bn1 of 64 channels (steve.py:180-182), and the stride-2 up-convolution restores the "
+                "input size while the position embedding is built for IMG_SIZE only when it is 64 (steve.py:189, :220)"
+                % (args.SLOTS.CNN_HID_SIZE, args.SLOTS.IMG_SIZE))
+        self.res18 = ResNet18()
         self.res18.conv1 = nn.Conv2d(args.SLOTS.IMG_CHANNELS, args.SLOTS.CNN_HID_SIZE, 3, 1, 1)
         self.fenc = nn.Sequential(*list(self.res18.children())[:-5])
         self.upconv = nn.ConvTranspose2d(args.SLOTS.CNN_HID_SIZE, args.SLOTS.DECODER.DIM, 3, stride=2, padding=1, dilation=1,
                                          output_padding=1)
+        self.hip_bn = os.environ.get("FOCUS_STEVE_BN", "1") != "0"
+
+    def _bn(self, bn, x, relu, residual=None):
+        """bn (an nn.BatchNorm2d, in its training / eval mode) -> act(bn(x) [+ residual])."""
+        if self.hip_bn:
+            if bn.training and bn.track_running_stats:
+                bn.num_batches_tracked.add_(1)                    # in place on the device, as nn.BatchNorm2d counts
+            return ops.batch_norm(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.training, bn.momentum, bn.eps,
+                                  relu=relu, residual=residual)
+        y = bn(x)
+        if residual is not None:
+            y = y + residual
+        return F.relu(y) if relu else y
 
     def forward(self, x):
-        return self.upconv(F.relu(self.fenc(x)))
+        conv1, bn1, _, pool, layer1 = self.fenc
+        x = self._bn(bn1, conv1(x), relu=True)
+        x = ops.max_pool_3x3_s2(x) if self.hip_bn else pool(x)
+        for blk in layer1:
+            out = self._bn(blk.bn1, blk.conv1(x), relu=True)
+            x = self._bn(blk.bn2, blk.conv2(out), relu=True, residual=x)
+        # (steve.py:202 applies F.relu once more: the identity on the output of a ReLU)
+        return self.upconv(x)
 
 
 def fetch_visual_encoder(args):
@@ -354,9 +440,26 @@ class STEVE(nn.Module):
         self.fused_rows = os.environ.get("FOCUS_STEVE_ROWS", "1") != "0"
         # FOCUS_STEVE_DECODE_CACHE=0: decode() re-runs the decoder over the whole prefix for every token (the reference's loop)
         self.decode_cache = os.environ.get("FOCUS_STEVE_DECODE_CACHE", "1") != "0"
+        # With the res18 trunk an evaluation-mode forward repeats bit for bit: there MIOpen is held to its deterministic
+        # convolution kernels (some of its kernels sum with atomics; measured: two eval passes of the dVAE encoder alone
+        # differ in the last bits).  Training, and the base encoder in both modes, keep MIOpen's own choice.
+        self.deterministic_eval = args.MODEL.CNN_NAME == "res18"
         if self.channels_last:
             self.dvae.to(memory_format=torch.channels_last)
             self.steve_encoder.cnn.to(memory_format=torch.channels_last)
+
+    @contextlib.contextmanager
+    def _repeatable(self):
+        """Around every convolution stack: see deterministic_eval."""
+        if self.training or not self.deterministic_eval:
+            yield
+            return
+        keep = torch.backends.cudnn.deterministic
+        torch.backends.cudnn.deterministic = True
+        try:
+            yield
+        finally:
+            torch.backends.cudnn.deterministic = keep
 
     def _conv(self, stack, x):
         """A convolution stack (dVAE decoder, CNN encoder; MIOpen) in the step's compute type: bf16 under
@@ -364,10 +467,11 @@ class STEVE(nn.Module):
         dVAE ENCODER stays fp32 in both modes: its output are the logits of a 4096-way softmax whose gradient is divided by
         tau, bf16 gains 8 % on that stack (the vocabulary projection dominates it) and costs a tenth of the gradient's
         accuracy (tests/test_gpu_steve.py); the sample it feeds the decoder is written in bf16 by the Gumbel kernel."""
-        if self.conv_dtype is None or not x.is_cuda:
-            return stack(x)
-        with torch.autocast("cuda", dtype=self.conv_dtype):
-            return stack(x)
+        with self._repeatable():
+            if self.conv_dtype is None or not x.is_cuda:
+                return stack(x)
+            with torch.autocast("cuda", dtype=self.conv_dtype):
+                return stack(x)
 
     def _frames(self, video):
         """[B,T,C,H,W] -> [B*T,C,H,W] in the memory format the convolutions run in."""
@@ -420,7 +524,9 @@ class STEVE(nn.Module):
         # dvae encode (:262-271).  The vocabulary axis is moved LAST: the rows of the channels-last logits are what the row
         # kernels read, and the ATen passes of the other branch run on a contiguous axis instead of as strided dim=1
         # ("spatial") kernels.  Same values; the decoder's 1x1 convolution receives the channels-last view (MIOpen's layout).
-        enc_out = self.dvae.encoder(video_flat).permute(0, 2, 3, 1)                       # B*T, H_enc, W_enc, vocab
+        with self._repeatable():
+            enc_out = self.dvae.encoder(video_flat)
+        enc_out = enc_out.permute(0, 2, 3, 1)                                            # B*T, H_enc, W_enc, vocab
         last = lambda e: None if e is None else e.permute(0, 2, 3, 1)
         e_soft, e_hard = last(noise.get("gumbel_soft")), last(noise.get("gumbel_hard"))
         rows = enc_out.reshape(-1, self.vocab_size)                                       # a view of channels-last logits
@@ -494,7 +600,8 @@ class STEVE(nn.Module):
                 z_gen = torch.cat((z_gen, z_next), dim=1)
                 input = torch.cat((input, dec.dict.dictionary(z_next)), dim=1)
         z_gen = F.one_hot(z_gen, self.vocab_size).transpose(1, 2).float().reshape(B, -1, H_enc, W_enc)
-        return self.dvae.decoder(z_gen).clamp(0.0, 1.0)
+        with self._repeatable():
+            return self.dvae.decoder(z_gen).clamp(0.0, 1.0)
 
     @torch.no_grad()
     def _generate_cached(self, slots, gen_len):

@@ -600,6 +600,50 @@ int focus_scale_add(const void* x, const void* y, const float* scale, float keep
 /* dtype conversion (weights shadow copies, gradient casts): n elements. */
 int focus_cast(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * BatchNorm2d and MaxPool2d(3, 2, 1) over channels-last feature maps (batchnorm.hip; the ResNet-18 trunk of STEVE,
+ * steve.py:175-202).  Every tensor is a row matrix [R, C], R = N*H*W, dense with row stride C; C % 8 == 0, 8 <= C <= 256;
+ * activations (x, y, residual, dy, dx, dres) in `dtype` (fp32 or bf16), statistics and affine parameters fp32.  A thread
+ * owns 8 consecutive channels (16-byte accesses); reductions over the rows are two-stage and in a fixed order (no atomics):
+ * the same inputs give the same bits.
+ *
+ * focus_bn_blocks(R): the number of row blocks of the reductions, >= 1 (host only).  focus_bn_workspace_bytes(R, C): the size
+ * of the caller-owned `workspace` of focus_bn_stats and focus_bn_bwd (host only; 0 for a C the kernels refuse).
+ *
+ * focus_bn_stats (training mode): mean[C] and rstd[C] = 1 / sqrt(var + eps), var the BIASED variance over the R rows.  Stage 1
+ *   leaves per-block (count, mean, M2) partials in the workspace (Welford: never E[x^2] - E[x]^2), stage 2 merges them
+ *   pairwise (Chan).  running_mean / running_var (both or neither; may be NULL) are updated in place:
+ *   r = (1 - momentum) r + momentum s, s the batch mean / the UNBIASED variance M2 / (R - 1), as nn.BatchNorm2d does.
+ *   R < 2 is FOCUS_ERR_SHAPE (torch raises there too).
+ * focus_bn_apply: y = act(gamma (x - mean) rstd + beta [+ residual]), act = ReLU (relu != 0) or the identity.  Eval mode is
+ *   the same call with mean / rstd formed from the running buffers.  residual may be NULL.
+ * focus_bn_bwd: g = dy (y > 0) when relu (the mask is read from the stored output y; y may be NULL otherwise), else g = dy;
+ *   dbeta = sum g, dgamma = sum g x^ (x^ = (x - mean) rstd); dx = gamma rstd (g - dbeta / R - x^ dgamma / R), or with
+ *   frozen != 0 (eval-mode statistics) dx = gamma rstd g; dres = g when dres is not NULL (the forward had a residual).
+ *
+ * focus_maxpool_fwd: x [N, H, W, C] -> y [N, OH, OW, C], OH = (H - 1) / 2 + 1, and idx [N, OH, OW, C] int8 = kh * 3 + kw of the
+ *   selected window position: the first maximum in row-major window order, padded positions skipped, a NaN counting as a
+ *   maximum (ATen's rule).  focus_maxpool_bwd: dx[n, h, w, c] = sum of dy over the <= 4 windows that cover (h, w) and whose
+ *   idx points at it (a gather: every element of dx is written once).
+ *
+ * Status, judged in this order before any launch: FOCUS_ERR_NULL (a required pointer is NULL; running_mean without
+ * running_var or the reverse; y NULL with relu in the backward), FOCUS_ERR_SHAPE (C % 8, C < 8, C > 256, R < 0, R < 2 for
+ * the statistics, N < 0, H < 1, W < 1, N*H*W >= 2^31 for the pool), FOCUS_ERR_DTYPE (neither fp32 nor bf16), FOCUS_ERR_ALIGN
+ * (any pointer not 16-byte aligned).  R == 0 / N == 0 is FOCUS_OK without a launch (focus_bn_bwd zero-fills dgamma and
+ * dbeta), except for focus_bn_stats.
+ * ----------------------------------------------------------------------------------------------*/
+int focus_bn_blocks(int64_t R);
+size_t focus_bn_workspace_bytes(int64_t R, int C);
+int focus_bn_stats(const void* x, float* mean, float* rstd, float* running_mean, float* running_var, void* workspace,
+                   int64_t R, int C, float eps, float momentum, int dtype, void* stream);
+int focus_bn_apply(const void* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                   const void* residual, void* y, int64_t R, int C, int relu, int dtype, void* stream);
+int focus_bn_bwd(const void* dy, const void* x, const void* y, const float* mean, const float* rstd, const float* gamma,
+                 void* dx, void* dres, float* dgamma, float* dbeta, void* workspace, int64_t R, int C, int relu,
+                 int frozen, int dtype, void* stream);
+int focus_maxpool_fwd(const void* x, void* y, void* idx, int N, int H, int W, int C, int dtype, void* stream);
+int focus_maxpool_bwd(const void* dy, const void* idx, void* dx, int N, int H, int W, int C, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
