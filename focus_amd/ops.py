@@ -2897,3 +2897,73 @@ def max_pool_3x3_s2(x):
     if x.dim() != 4:
         raise RuntimeError("focus_amd: max_pool_3x3_s2 takes [N,C,H,W] (got %d dimensions)" % x.dim())
     return _MaxPool3x3S2Fn.apply(x)
+
+
+# --------------------------------------------------------------------------------------------------
+# clip sampling: decoded uint8 clips -> model inputs (clip_sample.hip)
+# --------------------------------------------------------------------------------------------------
+CLIP_ITEM_INTS = ("H", "W", "sy0", "sx0", "sh", "sw", "rh", "rw", "oy0", "ox0", "flip")     # focus_clip_item after the pointer and strides
+
+
+def clip_items(clips, params, out_h, out_w):
+    """The host image of the focus_clip_item table of one launch: int64 [n, 9] (pointer, row and frame strides in bytes, then
+    the twelve int32 fields in pairs).  clips: uint8 CUDA tensors [T,H,W,3] with dense pixels (strides (*, *, 3, 1)) and one T;
+    params: one mapping per clip with sy0, sx0, sh, sw, rh, rw, oy0, ox0, flip.  A rectangle that leaves its frame, an empty
+    rectangle or virtual size, or a window that leaves the virtual image is a ValueError: the kernel cannot report it."""
+    import numpy as np
+    if len(clips) != len(params) or not clips:
+        raise ValueError("focus_amd: clip_sample takes one parameter set per clip and at least one clip")
+    _need_gpu(*clips)
+    T = clips[0].shape[0]
+    rec = np.zeros((len(clips), 9), dtype=np.int64)
+    for i, (c, p) in enumerate(zip(clips, params)):
+        if c.dtype != torch.uint8 or c.dim() != 4 or c.shape[3] != 3 or c.shape[0] != T or (c.numel() and c.stride()[2:] != (3, 1)):
+            raise ValueError("focus_amd: clip %d is not a uint8 [T,H,W,3] tensor with dense pixels and T = %d" % (i, T))
+        if c.device != clips[0].device:
+            raise ValueError("focus_amd: the clips of one launch live on one device")
+        H, W = int(c.shape[1]), int(c.shape[2])
+        v = dict(H=H, W=W, **{k: int(p[k]) for k in CLIP_ITEM_INTS[2:]})
+        v["flip"] = int(bool(p["flip"]))
+        if not (v["sh"] >= 1 and v["sw"] >= 1 and 0 <= v["sy0"] and v["sy0"] + v["sh"] <= H and 0 <= v["sx0"] and v["sx0"] + v["sw"] <= W):
+            raise ValueError("focus_amd: clip %d: source rectangle (y %d, x %d, h %d, w %d) is outside the %dx%d frame" % (
+                i, v["sy0"], v["sx0"], v["sh"], v["sw"], H, W))
+        if not (v["rh"] >= 1 and v["rw"] >= 1 and 0 <= v["oy0"] and v["oy0"] + out_h <= v["rh"] and 0 <= v["ox0"]
+                and v["ox0"] + out_w <= v["rw"]):
+            raise ValueError("focus_amd: clip %d: the %dx%d window at (%d, %d) is outside the resized %dx%d image" % (
+                i, out_h, out_w, v["oy0"], v["ox0"], v["rh"], v["rw"]))
+        rec[i, 0], rec[i, 1], rec[i, 2] = c.data_ptr(), c.stride(1), c.stride(0)
+        ints = [v[k] for k in CLIP_ITEM_INTS] + [0]
+        for k in range(6):
+            rec[i, 3 + k] = ints[2 * k] | (ints[2 * k + 1] << 32)
+    return rec
+
+
+def clip_sample(clips, params, out_h, out_w, mean, std, reverse=False, dtype=torch.float32, layout="BCTHW"):
+    """Decoded clips -> model inputs in ONE launch: per clip, crop the rectangle, resize it bilinearly (align_corners=False)
+    to (rh, rw), take the out_h x out_w window at (oy0, ox0), mirror it when flip, normalise (v/255 - mean) / std, reverse
+    the channels (after normalisation, as pack_pathway_output does) and cast.  layout "BCTHW" (Motionformer) or "BTCHW"
+    (STEVE).  One small H2D copy carries the descriptor table.  No CPU fallback."""
+    if layout not in ("BCTHW", "BTCHW"):
+        raise ValueError("focus_amd: clip_sample layout is BCTHW or BTCHW (got %r)" % (layout,))
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError("focus_amd: unsupported dtype %s (float32 or bfloat16)" % dtype)
+    if out_h < 1 or out_w < 1:
+        raise ValueError("focus_amd: clip_sample output size %dx%d" % (out_h, out_w))
+    if len(mean) != 3 or len(std) != 3 or any(float(s) == 0.0 for s in std):
+        raise ValueError("focus_amd: clip_sample takes three means and three non-zero stds")
+    rec = clip_items(clips, params, out_h, out_w)
+    dev, B, T = clips[0].device, len(clips), int(clips[0].shape[0])
+    plane = out_h * out_w
+    if layout == "BCTHW":
+        out = torch.empty(B, 3, T, out_h, out_w, device=dev, dtype=dtype)
+        sc, st = T * plane, plane
+    else:
+        out = torch.empty(B, T, 3, out_h, out_w, device=dev, dtype=dtype)
+        sc, st = plane, 3 * plane
+    mean3, std3 = (ctypes.c_float * 3)(*[float(m) for m in mean]), (ctypes.c_float * 3)(*[float(s) for s in std])
+    with torch.cuda.device(dev):
+        items = torch.from_numpy(rec).pin_memory().to(dev, non_blocking=True)
+        _lib.check(_lib.lib().focus_clip_sample(_p(items), B, T, out_h, out_w, _p(out), 3 * T * plane, sc, st,
+                                                ctypes.cast(mean3, ctypes.c_void_p), ctypes.cast(std3, ctypes.c_void_p),
+                                                int(bool(reverse)), _dt(out), _stream()), "clip_sample")
+    return out

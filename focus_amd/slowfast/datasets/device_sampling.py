@@ -1,0 +1,123 @@
+"""Clip sampling on the device: decoded uint8 clips and their boxes in, model inputs and `orvit_bboxes` out.
+
+The reference samples a clip on a loader worker (datasets/utils.py:111-188): float conversion, normalisation, a bilinear
+resize of the whole frame, a crop, a flip, the channel reversal.  All three of its modes -- short-side jitter + random crop,
+random resized crop (the branch every shipped ORViT config takes: AUG.ENABLE with TRAIN_JITTER_SCALES_RELATIVE), the test
+views 0/1/2 -- resize a source rectangle to (rh, rw) and take a window of the result, so here the HOST only draws the
+reference's random numbers and moves the boxes (`sampling_params`, bit-identical to the reference) and ONE HIP launch
+produces the pixels of the whole batch (`ops.clip_sample`).  RandAugment, colour jitter and random erasing are not part of
+this path."""
+import math
+
+import numpy as np
+import torch
+
+from ... import ops
+from . import transform
+from .utils import boxes_to_orvit_format
+
+
+def sampling_params(height, width, spatial_idx=-1, min_scale=256, max_scale=320, crop_size=224, random_horizontal_flip=True,
+                    inverse_uniform_sampling=False, aspect_ratio=None, scale=None, boxes=None):
+    """What datasets/utils.py:111-188 `spatial_sampling` would do to a [T,3,height,width] clip, without touching a pixel.
+    Consumes exactly the reference's draws for the chosen mode, in its order (numpy's and Python's global generators).
+    Returns (params, boxes): params holds the descriptor fields of ops.clip_sample (sy0, sx0, sh, sw, rh, rw, oy0, ox0, flip)
+    and out_h, out_w; boxes (numpy xyxy pixels, or None) are the reference's transformed boxes, bit for bit."""
+    assert spatial_idx in [-1, 0, 1, 2]
+    p = dict(sy0=0, sx0=0, sh=height, sw=width, rh=height, rw=width, oy0=0, ox0=0, flip=0, out_h=crop_size, out_w=crop_size)
+    if spatial_idx == -1 and not (aspect_ratio is None and scale is None):
+        # transform.random_resized_crop: the rectangle itself is resized to the crop size
+        i, j, h, w = transform._get_param_spatial_crop(scale, aspect_ratio, height, width)
+        p.update(sy0=i, sx0=j, sh=h, sw=w, rh=crop_size, rw=crop_size)
+        if boxes is not None:
+            boxes = transform.resized_crop_boxes(boxes, i, j, h, w, crop_size, crop_size)
+    else:
+        # transform.random_short_side_scale_jitter: the whole frame is resized (the test views draw their size too)
+        if spatial_idx != -1:
+            assert len({min_scale, max_scale}) == 1
+            inverse_uniform_sampling = False
+        if inverse_uniform_sampling:
+            size = int(round(1.0 / np.random.uniform(1.0 / max_scale, 1.0 / min_scale)))
+        else:
+            size = int(round(np.random.uniform(min_scale, max_scale)))
+        rh, rw = height, width
+        if not ((width <= height and width == size) or (height <= width and height == size)):
+            rh = rw = size
+            if width < height:
+                rh = int(math.floor((float(height) / width) * size))
+                if boxes is not None:
+                    boxes = boxes * float(rh) / height
+            else:
+                rw = int(math.floor((float(width) / height) * size))
+                if boxes is not None:
+                    boxes = boxes * float(rw) / width
+        if rh < crop_size or rw < crop_size:
+            raise ValueError("a %dx%d frame resized to %dx%d is smaller than the %d crop" % (height, width, rh, rw, crop_size))
+        if spatial_idx == -1:                                     # transform.random_crop
+            y_offset = x_offset = 0
+            if not (rh == crop_size and rw == crop_size):
+                if rh > crop_size:
+                    y_offset = int(np.random.randint(0, rh - crop_size))
+                if rw > crop_size:
+                    x_offset = int(np.random.randint(0, rw - crop_size))
+        else:                                                     # transform.uniform_crop
+            y_offset = int(math.ceil((rh - crop_size) / 2))
+            x_offset = int(math.ceil((rw - crop_size) / 2))
+            if rh > rw:
+                y_offset = {0: 0, 1: y_offset, 2: rh - crop_size}[spatial_idx]
+            else:
+                x_offset = {0: 0, 1: x_offset, 2: rw - crop_size}[spatial_idx]
+        p.update(rh=rh, rw=rw, oy0=y_offset, ox0=x_offset)
+        if boxes is not None and not (spatial_idx == -1 and rh == crop_size and rw == crop_size):
+            boxes = transform.crop_clip_boxes(boxes, x_offset, y_offset, crop_size)
+    if spatial_idx == -1 and random_horizontal_flip:             # transform.horizontal_flip(0.5, ...)
+        flipped = None if boxes is None else boxes.copy()
+        if np.random.uniform() < 0.5:
+            p["flip"] = 1
+            if boxes is not None:
+                flipped[..., [0, 2]] = crop_size - boxes[..., [2, 0]] - 1
+        boxes = flipped
+    return p, boxes
+
+
+def sample_clips(cfg, clips_u8, boxes, spatial_idx=-1, min_scale=None, max_scale=None, crop_size=None, aspect_ratio=None,
+                 scale=None, inverse_uniform_sampling=None, random_horizontal_flip=None):
+    """The hand-off between decoding and the model for one batch.  clips_u8: list of uint8 [T,H,W,3] CUDA tensors (H, W may
+    differ per clip); boxes: per clip a numpy [T,O,4] array of xyxy pixel boxes.  spatial_idx -1 samples for training (the
+    random resized crop when scale / aspect_ratio are given or the config carries DATA.TRAIN_JITTER_SCALES_RELATIVE /
+    TRAIN_JITTER_ASPECT_RELATIVE, else jitter + crop), 0/1/2 the test views; sizes default to the config's as in ssv2.py:243-276.
+    Returns (inputs, orvit_bboxes [B,T,O,4] float32 on the host): inputs [B,3,T,S,S] normalised with DATA.MEAN / DATA.STD and
+    channel-reversed per DATA.REVERSE_INPUT_CHANNEL, or for MODEL.MODEL_NAME "STEVE" [B,T,3,S,S] in [0,1]; bf16 under
+    TRAIN.MIXED_PRECISION, else fp32.  One H2D copy of the descriptor table, one kernel launch, no device round-trip."""
+    data = cfg.DATA
+    if spatial_idx == -1:
+        lo, hi = data.TRAIN_JITTER_SCALES
+        size = data.TRAIN_CROP_SIZE
+        if scale is None and aspect_ratio is None and len(getattr(data, "TRAIN_JITTER_SCALES_RELATIVE", [])):
+            scale, aspect_ratio = data.TRAIN_JITTER_SCALES_RELATIVE, data.TRAIN_JITTER_ASPECT_RELATIVE
+    else:
+        lo = hi = size = data.TEST_CROP_SIZE
+    min_scale = lo if min_scale is None else min_scale
+    max_scale = hi if max_scale is None else max_scale
+    crop_size = size if crop_size is None else crop_size
+    if inverse_uniform_sampling is None:
+        inverse_uniform_sampling = bool(getattr(data, "INV_UNIFORM_SAMPLE", False))
+    if random_horizontal_flip is None:
+        random_horizontal_flip = data.RANDOM_FLIP
+    if len(clips_u8) != len(boxes):
+        raise ValueError("sample_clips takes one box array per clip")
+    params, out_boxes = [], []
+    for clip, b in zip(clips_u8, boxes):
+        p, b = sampling_params(int(clip.shape[1]), int(clip.shape[2]), spatial_idx, min_scale, max_scale, crop_size,
+                               random_horizontal_flip, inverse_uniform_sampling, aspect_ratio, scale,
+                               np.array(b, dtype=np.float32))
+        params.append(p)
+        out_boxes.append(b)
+    dtype = torch.bfloat16 if cfg.TRAIN.MIXED_PRECISION else torch.float32
+    if cfg.MODEL.MODEL_NAME == "STEVE":
+        inputs = ops.clip_sample(clips_u8, params, crop_size, crop_size, [0.0] * 3, [1.0] * 3, False, dtype, "BTCHW")
+    else:
+        inputs = ops.clip_sample(clips_u8, params, crop_size, crop_size, data.MEAN, data.STD, data.REVERSE_INPUT_CHANNEL,
+                                 dtype, "BCTHW")
+    # one hand-off for the batch: boxes_to_orvit_format works box by box, so this is what B calls would give
+    return inputs, boxes_to_orvit_format(np.stack(out_boxes), crop_size, crop_size)

@@ -1,8 +1,10 @@
 """Spatial sampling of a clip together with its object boxes (mirror of slowfast/datasets/transform.py:42-294).
 Every function takes frames [T,C,H,W] on ANY device (the arithmetic is plain torch: the same call augments on the GPU
 when the decoded clip already lives there) and boxes [..., 4] xyxy in pixels as a numpy array or a tensor, and draws its
-random numbers with the reference's own numpy calls in the reference's order."""
+random numbers with the reference's own numpy calls in the reference's order (the resized crop also with Python's
+`random`, as the reference does)."""
 import math
+import random
 
 import numpy as np
 import torch
@@ -111,3 +113,57 @@ def clip_boxes_to_image(boxes, height, width):
     clipped[:, [0, 2]] = np.minimum(width - 1.0, np.maximum(0.0, boxes[:, [0, 2]]))
     clipped[:, [1, 3]] = np.minimum(height - 1.0, np.maximum(0.0, boxes[:, [1, 3]]))
     return clipped
+
+
+def _get_param_spatial_crop(scale, ratio, height, width, num_repeat=10, log_scale=True, switch_hw=False):
+    """transform.py:520-559: (i, j, h, w) of an Inception-style crop.  Per attempt: Python's random.uniform for the area
+    share and for the (log-)aspect ratio, ONE np.random.uniform() (the reference evaluates it on the left of
+    `and switch_hw`, so it is drawn whether or not it is used: leaving it out would shift every later flip), and two
+    random.randint for an accepted rectangle; after num_repeat rejected attempts the central crop."""
+    for _ in range(num_repeat):
+        area = height * width
+        target_area = random.uniform(*scale) * area
+        if log_scale:
+            log_ratio = (math.log(ratio[0]), math.log(ratio[1]))
+            aspect_ratio = math.exp(random.uniform(*log_ratio))
+        else:
+            aspect_ratio = random.uniform(*ratio)
+        w = int(round(math.sqrt(target_area * aspect_ratio)))
+        h = int(round(math.sqrt(target_area / aspect_ratio)))
+        if np.random.uniform() < 0.5 and switch_hw:
+            w, h = h, w
+        if 0 < w <= width and 0 < h <= height:
+            i = random.randint(0, height - h)
+            j = random.randint(0, width - w)
+            return i, j, h, w
+    in_ratio = float(width) / float(height)
+    if in_ratio < min(ratio):
+        w = width
+        h = int(round(w / min(ratio)))
+    elif in_ratio > max(ratio):
+        h = height
+        w = int(round(h * max(ratio)))
+    else:
+        w, h = width, height
+    return (height - h) // 2, (width - w) // 2, h, w
+
+
+def resized_crop_boxes(boxes, i, j, h, w, target_height, target_width):
+    """transform.py:596-599: boxes into the frame of the crop (i, j, h, w), clipped to it, scaled to the target size."""
+    boxes = crop_boxes(boxes, j, i)
+    boxes[..., [0, 2]] = np.clip(boxes[..., [0, 2]], 0, w) * float(target_width) / w
+    boxes[..., [1, 3]] = np.clip(boxes[..., [1, 3]], 0, h) * float(target_height) / h
+    return boxes
+
+
+def random_resized_crop(images, target_height, target_width, scale=(0.8, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), boxes=None):
+    """transform.py:562-602: a crop of random area share `scale` and aspect ratio `ratio`, resized to the target size;
+    numpy boxes follow it.  Returns images, or (images, boxes) when boxes are given.  (random_resized_crop_with_shift is
+    not mirrored: the reference forbids it with boxes.)"""
+    height, width = images.shape[2], images.shape[3]
+    i, j, h, w = _get_param_spatial_crop(scale, ratio, height, width)
+    ret = torch.nn.functional.interpolate(images[:, :, i:i + h, j:j + w], size=(target_height, target_width),
+                                          mode="bilinear", align_corners=False)
+    if boxes is not None:
+        return ret, resized_crop_boxes(boxes, i, j, h, w, target_height, target_width)
+    return ret

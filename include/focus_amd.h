@@ -644,6 +644,46 @@ int focus_bn_bwd(const void* dy, const void* x, const void* y, const float* mean
 int focus_maxpool_fwd(const void* x, void* y, void* idx, int N, int H, int W, int C, int dtype, void* stream);
 int focus_maxpool_bwd(const void* dy, const void* idx, void* dx, int N, int H, int W, int C, int dtype, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Clip sampling (clip_sample.hip): decoded uint8 clips -> model inputs in one launch.  The reference's three spatial
+ * sampling modes (datasets/utils.py:111-188: short-side jitter + random crop, random resized crop, the test views 0/1/2),
+ * its tensor_normalize (utils.py:319-336) and the channel reversal of pack_pathway_output (utils.py:86-87) are one
+ * operation: the source rectangle (sy0, sx0, sh, sw) of a frame is virtually resized to (rh, rw) with bilinear
+ * interpolation, align_corners=False, and the out_h x out_w window at offset (oy0, ox0) of that virtual image is
+ * written, mirrored in x when flip != 0.  For output pixel (y, x) of clip b, frame t, channel c:
+ *     xo = flip ? out_w-1-x : x
+ *     sy = max((y  + oy0 + 0.5f) * ((float)sh / rh) - 0.5f, 0);  y0 = min((int)sy, sh-1);  y1 = min(y0+1, sh-1);  ly = sy - y0
+ *     sx = max((xo + ox0 + 0.5f) * ((float)sw / rw) - 0.5f, 0);  x0, x1, lx likewise
+ *     v  = bilinear of src[t][sy0 + y{0,1}][sx0 + x{0,1}][c'] with (1-l, l) weights,  c' = reverse ? 2-c : c
+ *     out[b*sb + c*sc + t*st + y*out_w + x] = (v/255 - mean[c']) / std[c']          (fp32 arithmetic, one rounding to `dtype`)
+ * mean / std are indexed by the SOURCE channel: the reference reverses the channels after it has normalised them.
+ * Rows and planes of the output are dense (row stride out_w); sb, sc, st are the clip, channel and frame strides in
+ * elements, so one kernel writes [B,C,T,S,S] (Motionformer) and [B,T,C,S,S] (STEVE; mean 0, std 1 gives its [0,1] input).
+ *
+ * `items`: DEVICE array of n_clips descriptors owned by the caller; the clips of one launch may differ in everything a
+ * descriptor holds.  src is [T][H][W][3] uint8 with row_stride / frame_stride in BYTES (no alignment requirement: rows are
+ * read byte-wise).  `mean`, `std`: HOST pointers to 3 floats each, read before the call returns; std[c] != 0.  `out` has no
+ * alignment requirement beyond its element size (16-byte stores are used where the address allows them).  The same
+ * arguments give the same bits (no atomics, no workspace).
+ *
+ * The descriptors live on the device, so this entry point cannot judge them: the caller guarantees 0 <= sy0, sy0 + sh <= H,
+ * 0 <= sx0, sx0 + sw <= W, sh, sw, rh, rw >= 1 and 0 <= oy0, oy0 + out_h <= rh, 0 <= ox0, ox0 + out_w <= rw
+ * (focus_amd.ops.clip_sample raises ValueError otherwise).  The kernel clamps the rectangle to the frame before it reads,
+ * and skips a clip whose rectangle or virtual size is empty, so a bad descriptor cannot read outside [0,H) x [0,W).
+ *
+ * Status, judged in this order before any launch (a refused call writes nothing): FOCUS_ERR_NULL (items, out, mean or std is
+ * NULL); FOCUS_OK without a launch for n_clips <= 0 or T <= 0; FOCUS_ERR_SHAPE (out_h <= 0, out_w <= 0, T or n_clips above
+ * 65535); FOCUS_ERR_DTYPE (neither FOCUS_F32 nor FOCUS_BF16).
+ * ----------------------------------------------------------------------------------------------*/
+typedef struct focus_clip_item {
+    const uint8_t* src;
+    int64_t row_stride, frame_stride;
+    int32_t H, W, sy0, sx0, sh, sw, rh, rw, oy0, ox0, flip, pad_;
+} focus_clip_item;
+int focus_clip_sample(const focus_clip_item* items, int n_clips, int T, int out_h, int out_w, void* out,
+                      int64_t sb, int64_t sc, int64_t st, const float* mean, const float* std, int reverse, int dtype,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
