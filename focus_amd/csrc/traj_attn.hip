@@ -280,7 +280,7 @@ int space_logits(const SpaceDims& D, const void* qkv, void* L, int dtype, hipStr
 
 extern "C" size_t focus_traj_space_workspace_bytes(int B, int F, int P, int heads, int d, int dtype, int backward) {
     const size_t S = (size_t)F * P, N = S + 1, C = (size_t)heads * d, es = focus_esize(dtype);
-    const bool fused = focus_traj_space_mfma_ok(P, d, heads, dtype);
+    const bool fused = focus_traj_space_mfma_ok(F, P, d, heads, dtype);
     size_t bytes = (size_t)B * heads * N * es;               // cls row
     bytes += focus_traj_cls_scratch_floats(B, (int)N, heads) * sizeof(float) + 256;   // cls kernels' scratch (fwd and bwd)
     if (!fused) bytes += (size_t)B * heads * S * S * es;     // logits / probabilities (unfused path)
@@ -306,7 +306,7 @@ extern "C" int focus_traj_space_fwd(const void* qkv, void* xt, void* xdiag, void
     hipStream_t s = (hipStream_t)stream;
     SpaceDims D = {B, F, P, heads, d, F * P, F * P + 1, heads * d, 3 * (int64_t)heads * d};
     const float scale = 1.f / sqrtf((float)d);
-    const bool fused = focus_traj_space_mfma_ok(P, d, heads, dtype);
+    const bool fused = focus_traj_space_mfma_ok(F, P, d, heads, dtype);
     void* Lc = ws;                                           // cls row first, then the (unfused) S x S logits
     void* L = mptr(ws, (int64_t)B * heads * D.N, dtype);
     int rc;
@@ -365,7 +365,14 @@ extern "C" int focus_traj_space_bwd(const void* qkv, const void* xt, const void*
     hipStream_t s = (hipStream_t)stream;
     SpaceDims D = {B, F, P, heads, d, F * P, F * P + 1, heads * d, 3 * (int64_t)heads * d};
     const float scale = 1.f / sqrtf((float)d);
-    const bool fused = focus_traj_space_mfma_ok(P, d, heads, dtype);
+    const bool fused = focus_traj_space_mfma_ok(F, P, d, heads, dtype);
+    if (fused) {
+        // the fused kernels move these in 16-byte pieces (LDS-DMA, uint4): refused before the first launch, as in the forward
+        if (!xt) return FOCUS_ERR_NULL;
+        if (!focus_aligned(qkv, 16) || !focus_aligned(xt, 16) || !focus_aligned(dxt, 16) || !focus_aligned(dxdiag, 16) ||
+            !focus_aligned(dqkv, 16) || !focus_aligned(ws, 16))
+            return FOCUS_ERR_ALIGN;
+    }
     const int64_t nLL = fused ? 0 : (int64_t)B * heads * D.S * D.S, nLc = (int64_t)B * heads * D.N;
     const size_t es = focus_esize(dtype);
     void* Lc = ws;                        // cls probabilities

@@ -3,7 +3,10 @@
 // fused space-attention kernels: up to 14 blocks of 32 keys per frame (P <= 448: the HR 16x336 grid of 21x21 patches
 // + objects); the dQ kernel is instantiated per block count
 #define FOCUS_TRAJ_MAX_KEY_BLOCKS 14
-bool focus_traj_space_mfma_ok(int P, int d, int heads, int dtype);
+// ... and up to 16 frames: the size of the backward's per-wave lse table.  The route is decided once, from the whole
+// shape, so the workspace query, the forward and the backward always agree on it (more frames: the generic path)
+#define FOCUS_TRAJ_MAX_FRAMES 16
+bool focus_traj_space_mfma_ok(int F, int P, int d, int heads, int dtype);
 void focus_traj_space_tiling(int P, int* nkb, int* nt);
 int focus_traj_space_fwd_mfma(const void* qkv, void* xt, void* xdiag, float* lse, int B, int F, int P, int heads,
                               hipStream_t s);

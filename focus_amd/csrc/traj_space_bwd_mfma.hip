@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) void traj_dxsum_kernel(const bf16_t* __restric
     *reinterpret_cast<uint4*>(dxsum + g * 8) = o.u;
 }
 
-constexpr int MAXF = 16;     // frames the per-wave lse / delta tables are sized for
+constexpr int MAXF = FOCUS_TRAJ_MAX_FRAMES;     // frames the per-wave lse / delta tables are sized for
 
 // ------------------------------------------------------------------------------------------------
 // dQ.  Stream step t = (frame f, key block kb): ring stage t & 3 = [K block 32 x 128 B | V block 32 x 128 B]; wave w

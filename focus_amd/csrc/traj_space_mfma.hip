@@ -265,10 +265,10 @@ void focus_traj_space_tiling(int P, int* nkb, int* nt) {
     *nkb = k; *nt = NB / k;
 }
 
-bool focus_traj_space_mfma_ok(int P, int d, int heads, int dtype) {
+bool focus_traj_space_mfma_ok(int F, int P, int d, int heads, int dtype) {
     static const bool enabled = !(getenv("FOCUS_TRAJ_FUSED") && atoi(getenv("FOCUS_TRAJ_FUSED")) == 0);
     return enabled && dtype == FOCUS_BF16 && d == HD && P >= 1 && P <= 32 * FOCUS_TRAJ_MAX_KEY_BLOCKS &&
-           ((heads * HD) % 8) == 0;
+           F >= 1 && F <= FOCUS_TRAJ_MAX_FRAMES && ((heads * HD) % 8) == 0;
 }
 
 // Patch-token rows only (xt, xdiag, lse); the cls row is handled by the caller.

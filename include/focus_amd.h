@@ -210,7 +210,11 @@ size_t focus_traj_space_workspace_bytes(int B, int F, int P, int heads, int d, i
 int focus_traj_space_fwd(const void* qkv, void* xt, void* xdiag, void* cls_out, float* lse, float* cls_lse,
                          void* workspace, size_t workspace_bytes, int B, int F, int P, int heads, int d,
                          int dtype, void* stream);
-/* dqkv [B,N,3C] is fully written. dxt / dxdiag / dcls are the cotangents of xt / xdiag / cls_out. */
+/* dqkv [B,N,3C] is fully written. dxt / dxdiag / dcls are the cotangents of xt / xdiag / cls_out.
+ * The route is decided from the whole shape, the same way by the workspace query, the forward and the backward: the fused
+ * kernels take bf16, d = 64, P <= 448 and F <= 16, everything else the generic path.  On the fused route qkv, xt, xdiag
+ * (forward) and qkv, xt, dxt, dxdiag, dqkv and the workspace (backward) must be 16-byte aligned: FOCUS_ERR_ALIGN before
+ * anything is launched. */
 int focus_traj_space_bwd(const void* qkv, const void* xt, const void* cls_out, const float* lse,
                          const float* cls_lse, const void* dxt, const void* dxdiag, const void* dcls,
                          void* dqkv, void* workspace, size_t workspace_bytes, int B, int F, int P,

@@ -87,6 +87,49 @@ def test_row_kernels_validate_before_launching(built):
     assert torch.equal(ops.dropout_add(x, x, 0.1, False), x + x)          # evaluation: the plain sum, any device
 
 
+def test_space_attention_validates_before_launching(built):
+    """focus_traj_space_fwd / _bwd refuse bad arguments with the ABI's codes before any launch (host pointers, no GPU), and
+    the workspace query, the forward and the backward decide the route from the same whole shape."""
+    from focus_amd import _lib
+    lib = _lib.lib()
+    F32, BF16 = _lib.F32, _lib.BF16
+    NULL, SHAPE, ALIGN, WORKSPACE = -5, -1, -3, -6
+    buf = ctypes.create_string_buffer(1 << 12)
+    a = ctypes.addressof(buf)
+    a += -a % 16
+    ptr, odd = ctypes.c_void_p(a), ctypes.c_void_p(a + 8)
+    dims = (2, 2, 33, 3, 64, BF16)                                   # B, F, P, heads, d, dtype: the fused route
+    nf, nb = (lib.focus_traj_space_workspace_bytes(*dims, bw) for bw in (0, 1))
+    # ---- the route: one decision for all three.  Fused: no S x S logits; F > 16, P > 448, fp32: the generic path's ----
+    S = 2 * 33
+    logits = 2 * 3 * S * S * 2
+    assert nf < logits and nb < 2 * logits                           # the generic backward: two S x S buffers and more
+    for F_, P, dt, es in ((17, 3, BF16, 2), (17, 40, BF16, 2), (16, 449, BF16, 2), (2, 33, F32, 4)):
+        one = 2 * 3 * (F_ * P) ** 2 * es
+        assert lib.focus_traj_space_workspace_bytes(2, F_, P, 3, 64, dt, 0) >= one, (F_, P)
+        assert lib.focus_traj_space_workspace_bytes(2, F_, P, 3, 64, dt, 1) >= 2 * one, (F_, P)
+    assert lib.focus_traj_space_workspace_bytes(2, 16, 40, 3, 64, BF16, 1) < 2 * 3 * 640 * 640 * 2           # F = 16 is fused
+    # ---- forward: qkv, xt, xdiag, cls_out, lse, cls_lse, workspace ----
+    fwd = [ptr] * 7
+    for i in range(7):
+        assert lib.focus_traj_space_fwd(*(fwd[:i] + [None] + fwd[i + 1:]), nf, *dims, None) == NULL, i
+    for bad in ((0, 2, 33, 3, 64), (2, 0, 33, 3, 64), (2, 2, 0, 3, 64), (2, 2, 33, 0, 64), (2, 2, 33, 3, 0), (2, 2, 33, 3, 62)):
+        assert lib.focus_traj_space_fwd(*fwd, 1 << 40, *bad, BF16, None) == SHAPE, bad
+    assert lib.focus_traj_space_fwd(*fwd, nf - 1, *dims, None) == WORKSPACE
+    for i in (0, 1, 2):
+        assert lib.focus_traj_space_fwd(*(fwd[:i] + [odd] + fwd[i + 1:]), nf, *dims, None) == ALIGN, i
+    # ---- backward: qkv, xt, cls_out, lse, cls_lse, dxt, dxdiag, dcls, dqkv, workspace ----
+    bwd = [ptr] * 10
+    for i in (0, 1, 3, 4, 5, 6, 7, 8, 9):                            # (cls_out is not read)
+        assert lib.focus_traj_space_bwd(*(bwd[:i] + [None] + bwd[i + 1:]), nb, *dims, None) == NULL, i
+    for bad in ((0, 2, 33, 3, 64), (2, 0, 33, 3, 64), (2, 2, 0, 3, 64), (2, 2, 33, 0, 64), (2, 2, 33, 3, 0), (2, 2, 33, 3, 62)):
+        assert lib.focus_traj_space_bwd(*bwd, 1 << 40, *bad, BF16, None) == SHAPE, bad
+    assert lib.focus_traj_space_bwd(*bwd, nb - 1, *dims, None) == WORKSPACE
+    for i in (0, 1, 5, 6, 8, 9):                                     # what moves in 16-byte pieces
+        assert lib.focus_traj_space_bwd(*(bwd[:i] + [odd] + bwd[i + 1:]), nb, *dims, None) == ALIGN, i
+    assert bytes(buf) == bytes(1 << 12)                              # and nothing was written
+
+
 def test_config_and_registry_surface():
     from focus_amd.slowfast.config.defaults import assert_and_infer_cfg, get_cfg
     from focus_amd.slowfast.models import MODEL_REGISTRY, build_model

@@ -57,7 +57,7 @@ def test_hr_shapes_take_the_fused_kernels():
     assert L.focus_traj_space_workspace_bytes(1, 8, 441, 12, 64, _lib.F32, 0) >= 12 * 3528 * 3528 * 4
 
 
-@pytest.mark.parametrize("P,F_", [(225, 2), (257, 3), (300, 2), (352, 2), (441, 2), (447, 3), (448, 2)])
+@pytest.mark.parametrize("P,F_", [(225, 2), (257, 3), (300, 2), (352, 2), (384, 2), (416, 2), (441, 2), (447, 3), (448, 2)])
 def test_space_attention_key_tilings(oracle, P, F_):
     """Every key tiling the dispatcher can pick for 224 < P <= 448 (8..14 key blocks: 2x4, 3x3, 2x5, 11x1, 2x7 ...),
     ragged last blocks included, bf16 fused kernels against the oracle on bf16-rounded inputs (fp64 arithmetic):
