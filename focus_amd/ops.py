@@ -2967,3 +2967,95 @@ def clip_sample(clips, params, out_h, out_w, mean, std, reverse=False, dtype=tor
                                                 ctypes.cast(mean3, ctypes.c_void_p), ctypes.cast(std3, ctypes.c_void_p),
                                                 int(bool(reverse)), _dt(out), _stream()), "clip_sample")
     return out
+
+
+# --------------------------------------------------------------------------------------------------
+# Mixup / CutMix on the device (datasets/mixup.py:40-192) and the soft-target loss (losses.py:15-36): csrc/mixup.hip
+# --------------------------------------------------------------------------------------------------
+def _need_dense(x, what):
+    _need_gpu(x)
+    if not x.is_contiguous():
+        raise ValueError("focus_amd: %s works in place on a contiguous tensor (mixing a copy would leave the "
+                         "caller's tensor unmixed); got strides %s for shape %s" % (what, tuple(x.stride()), tuple(x.shape)))
+
+
+def mixup_blend_(x, lam):
+    """x <- x * lam + x.flip(0) * (1 - lam) in place, with the bits of ATen's `x.flip(0).mul_(1 - lam)`,
+    `x.mul_(lam).add_(...)` (three separately rounded operations), in one pass and without the flipped copy.
+    x: [B, ...] fp32 or bf16, contiguous.  Returns x itself.  No CPU fallback."""
+    _need_dense(x, "mixup_blend_")
+    if x.dim() < 1 or x.numel() == 0:
+        raise ValueError("focus_amd: mixup_blend_ needs a non-empty [B, ...] tensor")
+    lam = float(lam)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().focus_mixup_blend(_p(x), x.shape[0], x.numel() // x.shape[0], lam, 1.0 - lam, _dt(x),
+                                                _stream()), "mixup_blend")
+    return x
+
+
+def cutmix_paste_(x, yl, yh, xl, xh):
+    """x[..., yl:yh, xl:xh] = x.flip(0)[..., yl:yh, xl:xh] in place, as a swap of the rectangle between samples i and
+    B-1-i.  x: [B, ..., H, W] fp32 or bf16, contiguous ([B,3,T,H,W] and [B,T,3,H,W] alike).  Returns x itself."""
+    _need_dense(x, "cutmix_paste_")
+    if x.dim() < 3 or x.numel() == 0:
+        raise ValueError("focus_amd: cutmix_paste_ needs a non-empty [B, ..., H, W] tensor")
+    yl, yh, xl, xh = int(yl), int(yh), int(xl), int(xh)
+    B, H, W = x.shape[0], x.shape[-2], x.shape[-1]
+    if not (0 <= yl <= yh <= H and 0 <= xl <= xh <= W):
+        raise ValueError("focus_amd: cutmix box y %d:%d x %d:%d outside the %dx%d frame" % (yl, yh, xl, xh, H, W))
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().focus_cutmix_paste(_p(x), B, x.numel() // (B * H * W), H, W, yl, yh, xl, xh, _dt(x),
+                                                 _stream()), "cutmix_paste")
+    return x
+
+
+def mixup_target(labels, num_classes, lam=1.0, smoothing=0.0):
+    """Dense fp32 [B, num_classes] target of mixup.py:40-64 in one launch: smoothed one-hot rows of `labels` and of
+    `labels.flip(0)`, mixed with lam / 1 - lam.  labels: [B] integer class indices on the device."""
+    _need_gpu(labels)
+    num_classes = int(num_classes)
+    if labels.dim() != 1 or labels.numel() < 1 or num_classes < 1 or labels.is_floating_point():
+        raise ValueError("focus_amd: mixup_target takes [B] integer labels and num_classes >= 1")
+    labels = labels.long().contiguous()
+    off = smoothing / num_classes
+    on = 1.0 - smoothing + off
+    lam = float(lam)
+    target = torch.empty(labels.shape[0], num_classes, device=labels.device, dtype=torch.float32)
+    with torch.cuda.device(labels.device):
+        _lib.check(_lib.lib().focus_mixup_target(_p(labels), _p(target), labels.shape[0], num_classes, on, off, lam,
+                                                 1.0 - lam, _stream()), "mixup_target")
+    return target
+
+
+class _XentSoftFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, mean):
+        R, V = logits.shape
+        x = logits.float().contiguous()
+        loss_rows = torch.empty(R, device=logits.device, dtype=torch.float32)
+        dlog = torch.empty_like(x)
+        _lib.check(_lib.lib().focus_xent_soft(_p(x), _p(target), _p(loss_rows), _p(dlog), R, V, _stream()), "xent_soft")
+        ctx.save_for_backward(dlog)
+        ctx.mean, ctx.dtype = mean, logits.dtype
+        return loss_rows.mean() if mean else loss_rows
+
+    @staticmethod
+    def backward(ctx, g):
+        (dlog,) = ctx.saved_tensors                 # d(mean over rows) / d(logits)
+        g = g.float()
+        d = dlog * g if ctx.mean else dlog * (g * dlog.shape[0])[:, None]
+        return d.to(ctx.dtype), None, None
+
+
+def soft_target_ce(logits, target, reduction="mean"):
+    """sum(-target * log_softmax(logits), -1) with its gradient from one row kernel; reduction "mean" or "none".
+    logits [R,V] fp32 or bf16 (widened first; the gradient comes back in the logits' type), target [R,V] (used as fp32;
+    the rows need not sum to 1, no gradient flows into it)."""
+    _need_gpu(logits, target)
+    if reduction not in ("mean", "none"):
+        raise ValueError("focus_amd: soft_target_ce reduction is 'mean' or 'none' (got %r)" % (reduction,))
+    if logits.dim() != 2 or logits.shape != target.shape or logits.numel() == 0:
+        raise ValueError("focus_amd: soft_target_ce takes logits and target of one [R,V] shape (got %s and %s)" %
+                         (tuple(logits.shape), tuple(target.shape)))
+    _dt(logits)
+    return _XentSoftFn.apply(logits, target.detach().float().contiguous(), reduction == "mean")

@@ -1,10 +1,24 @@
-"""Loss lookup (mirror of slowfast/models/losses.py:40-121): label-smoothing / plain cross entropy on the fused
-focus_xent_ls kernel, and the EPIC-Kitchens verb+noun wrapper (EKLoss, losses.py:62-95)."""
+"""Loss lookup (mirror of slowfast/models/losses.py:15-121): label-smoothing / plain cross entropy on the fused
+focus_xent_ls kernel, soft-target cross entropy (mixup / cutmix targets) on focus_xent_soft, and the EPIC-Kitchens
+verb+noun wrapper (EKLoss, losses.py:62-95)."""
 from functools import partial
 
 import torch.nn as nn
 
 from focus_amd import ops
+
+
+class SoftTargetCrossEntropy(nn.Module):
+    """losses.py:15-36: sum(-y * log_softmax(x)) per row against a dense [B,V] target; reduction "mean" or "none"."""
+
+    def __init__(self, reduction="mean"):
+        super().__init__()
+        self.reduction = reduction
+
+    def forward(self, x, y):
+        if self.reduction not in ("mean", "none"):
+            raise NotImplementedError
+        return ops.soft_target_ce(x, y, self.reduction)
 
 
 class LabelSmoothingCrossEntropy(nn.Module):
@@ -28,7 +42,7 @@ class EKLoss(nn.Module):
         super().__init__()
         self.reduction = reduction
         if ce_type == "soft":
-            raise NotImplementedError("soft-target CE (mixup) is outside the hot-path configs (MIXUP.ENABLE False)")
+            self.ce_loss = SoftTargetCrossEntropy(reduction=reduction)
         elif ce_type == "label_smoothing":
             self.ce_loss = LabelSmoothingCrossEntropy(reduction=reduction, smoothing=smoothing)
         else:
@@ -40,6 +54,7 @@ class EKLoss(nn.Module):
 
 
 _LOSSES = {"cross_entropy": partial(LabelSmoothingCrossEntropy, smoothing=0.0),
+           "soft_cross_entropy": SoftTargetCrossEntropy,
            "label_smoothing_cross_entropy": LabelSmoothingCrossEntropy}
 
 
@@ -50,6 +65,8 @@ def get_loss_func(cfg, state="train"):
     if cfg.TRAIN.DATASET == "epickitchens":                       # losses.py:106-114
         if name == "cross_entropy":
             return partial(EKLoss, ce_type="")
+        if name == "soft_cross_entropy":
+            return partial(EKLoss, ce_type="soft")
         if name == "label_smoothing_cross_entropy":
             return partial(EKLoss, ce_type="label_smoothing", smoothing=cfg.MIXUP.LABEL_SMOOTH_VALUE)
         raise NotImplementedError("%s for epickitchens" % name)

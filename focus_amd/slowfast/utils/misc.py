@@ -1,4 +1,4 @@
-"""Hot-loop helpers and the job launcher (mirror of slowfast/utils/misc.py:26-33, 285-313, 388-398)."""
+"""Hot-loop helpers and the job launcher (mirror of slowfast/utils/misc.py:26-33, 285-313, 388-398, 417-421)."""
 import math
 
 import torch
@@ -37,3 +37,8 @@ def iter_to_cuda(batch):
             return {k: _to(v) for k, v in x.items()}
         return x
     return _to(batch)
+
+
+def get_num_classes(cfg):
+    """misc.py:417-421: the EPIC-Kitchens heads have their own class counts, keyed like the label dict."""
+    return {"verb": 97, "noun": 300} if cfg.TRAIN.DATASET == "epickitchens" else cfg.MODEL.NUM_CLASSES

@@ -38,6 +38,56 @@ def train_step(model, optimizer, loss_fun, inputs, labels, meta, cfg, check_nan=
     return preds, loss
 
 
+def build_mixup(cfg):
+    """The MixUp object of train_net.py:58-66, or None when MIXUP.ENABLE is off."""
+    if not cfg.MIXUP.ENABLE:
+        return None
+    from .slowfast.datasets.mixup import MixUp
+    return MixUp(mixup_alpha=cfg.MIXUP.ALPHA, cutmix_alpha=cfg.MIXUP.CUTMIX_ALPHA, mix_prob=cfg.MIXUP.PROB,
+                 switch_prob=cfg.MIXUP.SWITCH_PROB, label_smoothing=cfg.MIXUP.LABEL_SMOOTH_VALUE,
+                 num_classes=misc.get_num_classes(cfg))
+
+
+def mixup_collapse(preds, labels):
+    """train_net.py:123-149: fold mixed dense labels back for the top-k metrics.  Per head, the two largest entries of a
+    label row are the mixed pair: the runner-up's score is added into the winner's column of a detached copy of the
+    predictions and then zeroed, and the label becomes the winner's index.  Tensors, or the EK dicts of them (`preds` is
+    then the {'verb','noun'} logits dict).  [B,V] logging work in plain torch; ties in a label row have no defined order."""
+    if isinstance(labels, dict):
+        pairs = {k: mixup_collapse(preds[k], labels[k]) for k in labels}
+        return {k: p for k, (p, _) in pairs.items()}, {k: l for k, (_, l) in pairs.items()}
+    top2 = torch.topk(labels, 2, dim=1, largest=True, sorted=True).indices
+    rows = torch.arange(labels.shape[0], device=preds.device)
+    first, second = top2[:, 0].to(preds.device), top2[:, 1].to(preds.device)
+    preds = preds.detach().clone()
+    preds[rows, first] += preds[rows, second]
+    preds[rows, second] = 0.0
+    return preds, top2[:, 0]
+
+
+def train_iter(model, optimizer, loss_fun, inputs, labels, meta, cfg, mixup_fn=None, check_nan=True):
+    """One iteration of train_net.py:78-149 around the unchanged train_step: the optional mixup of inputs[0] and the labels
+    (:78-80), the step (:82-121), and with mixup the collapse of the dense labels for the metrics (:123-149).  Returns
+    (preds, labels, loss) ready for metrics.topk_errors; for epickitchens `preds` is the {'verb','noun'} dict when mixing
+    was on (what the reference scores there), else what train_step returned."""
+    if mixup_fn is not None:
+        inputs[0], labels = mixup_fn(inputs[0], labels)
+    if mixup_fn is None or cfg.TRAIN.DATASET != "epickitchens":
+        preds, loss = train_step(model, optimizer, loss_fun, inputs, labels, meta, cfg, check_nan=check_nan)
+    else:
+        # train_step hands back the verb logits alone; the collapse needs both heads, so keep the forward's dict
+        kept = {}
+        hook = model.register_forward_hook(lambda _m, _i, out: kept.update(out[1]) if isinstance(out, tuple) else None)
+        try:
+            preds, loss = train_step(model, optimizer, loss_fun, inputs, labels, meta, cfg, check_nan=check_nan)
+        finally:
+            hook.remove()
+        preds = kept
+    if mixup_fn is not None:
+        preds, labels = mixup_collapse(preds, labels)
+    return preds, labels, loss
+
+
 def slot_train_step(model, optimizer, video, global_step, cfg, noise=None):
     """One iteration of slot_train_epoch (tools/steve_train_net.py:57-126): schedules -> forward -> mse + cross_entropy ->
     NaN check -> zero_grad -> backward -> clip-norm -> step.  Returns (loss, mse, cross_entropy, recon, attns, tau).

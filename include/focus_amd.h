@@ -688,6 +688,42 @@ int focus_clip_sample(const focus_clip_item* items, int n_clips, int T, int out_
                       int64_t sb, int64_t sc, int64_t st, const float* mean, const float* std, int reverse, int dtype,
                       void* stream);
 
+/* -------------------------------------------------------------------------------------------------
+ * Mixup / CutMix of a batch of clips and the soft-target loss that goes with them (mixup.hip; datasets/mixup.py:40-192 and
+ * losses.py:15-36 of the reference).  Sample i of the batch is always paired with sample B-1-i (x.flip(0)).  r() below is
+ * one round-to-nearest-even to the tensor's type; all arithmetic runs in fp32 and is never contracted into an fma, so the
+ * results carry the bits of ATen's separately rounded mul_ / mul_ / add_.  lam and one_minus_lam are the fp32 roundings of
+ * the host doubles lam and 1.0 - lam.  No workspace, no atomics: the same call gives the same bits.
+ *
+ * focus_mixup_blend: x [B, n_per_sample] contiguous, in place:
+ *     x[i] <- r(r(x[i] lam) + r(x[B-1-i] oml)),   x[B-1-i] <- r(r(x[B-1-i] lam) + r(x[i] oml))
+ *   both computed from the values loaded before either is stored; the middle sample of an odd batch pairs with itself:
+ *   r(r(a lam) + r(a oml)).  16-byte accesses when x is 16-byte aligned and n_per_sample * elemsize % 16 == 0, else scalar.
+ *   Status in this order: FOCUS_ERR_NULL (x); FOCUS_ERR_SHAPE (B < 1, n_per_sample < 1); FOCUS_ERR_DTYPE (neither fp32 nor
+ *   bf16); FOCUS_ERR_ALIGN (x not aligned to its element size).
+ *
+ * focus_cutmix_paste: x [B, M, H, W] contiguous, in place: the rectangle [yl,yh) x [xl,xh) of every plane is swapped
+ *   between samples i and B-1-i (x[..., yl:yh, xl:xh] = x.flip(0)[..., yl:yh, xl:xh]); the middle sample of an odd batch
+ *   and every byte outside the rectangle are not touched.  Status in this order: FOCUS_ERR_NULL (x); FOCUS_ERR_SHAPE
+ *   (B, M, H or W < 1, yl < 0, yh > H, yl > yh, xl < 0, xh > W, xl > xh); FOCUS_ERR_DTYPE; FOCUS_ERR_ALIGN (as above);
+ *   FOCUS_OK without a launch for an empty rectangle or B == 1.
+ *
+ * focus_mixup_target: labels [B] int64 -> target [B,V] fp32,
+ *     target[b,c] = r(r(t1 lam) + r(t2 oml)),  t1 = c == labels[b] ? on : off,  t2 = c == labels[B-1-b] ? on : off.
+ *   A label outside [0,V) matches no column.  Status: FOCUS_ERR_NULL (labels, target); FOCUS_ERR_SHAPE (B < 1, V < 1).
+ *
+ * focus_xent_soft: logits, target [R,V] fp32 -> loss_rows [R] = lse sum(y) - sum(y x) = sum(-y log_softmax(x)) and
+ *   dlogits [R,V] = (softmax(x) sum(y) - y) / R, the gradient of the mean over rows.  Targets need not sum to 1.  One
+ *   256-thread workgroup per row, any V >= 1.  Status: FOCUS_ERR_NULL (any pointer); FOCUS_ERR_SHAPE (R < 1, V < 1).
+ * ----------------------------------------------------------------------------------------------*/
+int focus_mixup_blend(void* x, int64_t B, int64_t n_per_sample, float lam, float one_minus_lam, int dtype, void* stream);
+int focus_cutmix_paste(void* x, int64_t B, int64_t M, int H, int W, int yl, int yh, int xl, int xh, int dtype,
+                       void* stream);
+int focus_mixup_target(const int64_t* labels, float* target, int B, int V, float on, float off, float lam,
+                       float one_minus_lam, void* stream);
+int focus_xent_soft(const float* logits, const float* target, float* loss_rows, float* dlogits, int R, int V,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif
