@@ -59,6 +59,12 @@ class FlashArgs(ctypes.Structure):
                 [("drop_thr", ctypes.c_uint32), ("scale", ctypes.c_float), ("pad_", ctypes.c_int32)])
 
 
+class OptimHyper(ctypes.Structure):
+    _fields_ = [("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("momentum", ctypes.c_double), ("dampening", ctypes.c_double),
+                ("eps", ctypes.c_float), ("max_norm", ctypes.c_float), ("clip_value", ctypes.c_float),
+                ("nesterov", ctypes.c_int32), ("write_clipped_grads", ctypes.c_int32), ("pad_", ctypes.c_int32)]
+
+
 _CTYPE = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64,
           "size_t": ctypes.c_size_t, "float": ctypes.c_float, "double": ctypes.c_double}
 

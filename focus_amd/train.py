@@ -26,10 +26,16 @@ def train_step(model, optimizer, loss_fun, inputs, labels, meta, cfg, check_nan=
         misc.check_nan_losses(float(loss.detach()))                        # :102 (host sync, as in the reference)
     optimizer.zero_grad(set_to_none=True)                         # :105
     loss.backward()                                               # :106
-    if cfg.SOLVER.CLIP_GRAD_VAL:
+    from .slowfast.models import optimizer as optim
+    fused = optim.fused_route(model, optimizer)                   # FusedAdam / FusedSGD holding every trainable parameter
+    if cfg.SOLVER.CLIP_GRAD_VAL and fused:
+        optimizer.step_clipped(clip_value=cfg.SOLVER.CLIP_GRAD_VAL)                         # :108-111 + :120 in one pass
+        return preds, loss
+    elif cfg.SOLVER.CLIP_GRAD_VAL:
         torch.nn.utils.clip_grad_value_(model.parameters(), cfg.SOLVER.CLIP_GRAD_VAL)      # :108-111
-    elif cfg.SOLVER.CLIP_GRAD_L2NORM and hasattr(optimizer, "step_clipped"):
-        # :112-120 as one multi-tensor pass (optimizer.FusedAdamW: norm, clip, AdamW, bf16 shadows; csrc/optim.hip)
+    elif cfg.SOLVER.CLIP_GRAD_L2NORM and hasattr(optimizer, "step_clipped") and (
+            fused or not isinstance(optimizer, (optim.FusedAdam, optim.FusedSGD))):
+        # :112-120 as one multi-tensor pass (optimizer.Fused*: norm, clip, update, bf16 shadows; csrc/optim.hip)
         optimizer.step_clipped(cfg.SOLVER.CLIP_GRAD_L2NORM)
         return preds, loss
     elif cfg.SOLVER.CLIP_GRAD_L2NORM:
@@ -109,6 +115,13 @@ def slot_train_step(model, optimizer, video, global_step, cfg, noise=None):
     misc.check_nan_losses(float(loss.detach()))                                                       # :108
     optimizer.zero_grad()                                                                             # :111
     loss.backward()
+    if (cfg.SOLVER.CLIP_GRAD_VAL or cfg.SOLVER.CLIP_GRAD_L2NORM) and optim.fused_route(model, optimizer):
+        # :116-126 as one multi-tensor pass (optimizer.FusedAdam / FusedSGD: clip, update, bf16 shadows; csrc/optim.hip)
+        if cfg.SOLVER.CLIP_GRAD_VAL:
+            optimizer.step_clipped(clip_value=cfg.SOLVER.CLIP_GRAD_VAL)
+        else:
+            optimizer.step_clipped(max_norm=cfg.SOLVER.CLIP_GRAD_L2NORM)
+        return loss, mse, cross_entropy, recon, attns, tau
     if cfg.SOLVER.CLIP_GRAD_VAL:                                                                      # :116-123
         torch.nn.utils.clip_grad_value_(model.parameters(), cfg.SOLVER.CLIP_GRAD_VAL)
     elif cfg.SOLVER.CLIP_GRAD_L2NORM:

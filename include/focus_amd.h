@@ -424,6 +424,40 @@ int focus_adamw_step(const focus_adamw_item* items, float* const* grads, int n_i
                      void* workspace, size_t workspace_bytes, float* total_norm, double beta1, double beta2, float eps,
                      float max_norm, int write_clipped_grads, void* stream);
 
+/* The same two launches for the three update rules of the training loops (train_net.py:108-120, steve_train_net.py:116-126):
+ * focus_adamw_step is this entry with mode FOCUS_OPTIM_ADAMW.  Items, gradient pointers, group table, step counters,
+ * workspace and the bf16 copies are those of focus_adamw_step.  Per element, in fp32 (coef = the norm-clip coefficient, 1
+ * without clipping; 1 - beta, bc1 = 1 - beta1^step and bc2 = 1 - beta2^step are formed in double):
+ *   ADAMW  torch.optim.AdamW:  g = coef*g;  p -= lr*wd*p;  m += (1-b1)*(g-m);  v = b2*v + (1-b2)*g*g;
+ *          p -= (lr/bc1) * (m / (sqrt(v)*(1/sqrt(bc2)) + eps))
+ *   ADAM   torch.optim.Adam without amsgrad (coupled decay):  g = coef*g;  if wd: g += wd*p;  then m, v and p as above
+ *          without the decoupled decay
+ *   SGD    torch.optim.SGD:  g = coef*g;  if wd: g += wd*p;  with momentum > 0 and a buffer (item.m):
+ *          buf = g on the buffer's FIRST use (no dampening, as torch does), buf = momentum*buf + (1-dampening)*g afterwards;
+ *          g = g + momentum*buf with nesterov, else g = buf;  then p -= lr*g.
+ *          item.v is not read; with momentum == 0 item.m is not read either (both may be NULL).
+ * First use is a property of the buffer, not of the global step: steps[i] counts the uses of item i's buffer, the call
+ * increments it, and the use that takes it to 1 is the first.  The caller starts a fresh buffer's counter at 0 (whenever
+ * its first gradient arrives) and the counter of a buffer that comes from a checkpoint at >= 1.  For ADAM / ADAMW steps[i]
+ * is the `step` of the bias corrections.
+ * clip_value > 0: g is clamped to +-clip_value before anything else (clip_grad_value_, SOLVER.CLIP_GRAD_VAL); it excludes
+ * max_norm > 0.  write_clipped_grads stores the clamped / scaled g back (scaled: only when coef < 1).  `total_norm` always
+ * receives the norm of the gradients as they arrived.
+ * Status, judged in this order before any launch (a refused call writes nothing): FOCUS_ERR_NULL (items, grads, groups,
+ * steps, workspace or hyper is NULL); FOCUS_ERR_SHAPE (an unknown mode; max_norm > 0 together with clip_value > 0; SGD
+ * with nesterov and momentum <= 0 or dampening != 0); FOCUS_OK without a launch for n_items <= 0 or n_units <= 0;
+ * FOCUS_ERR_WORKSPACE (fewer than focus_adamw_workspace_bytes()). */
+enum focus_optim_mode { FOCUS_OPTIM_ADAMW = 0, FOCUS_OPTIM_ADAM = 1, FOCUS_OPTIM_SGD = 2 };
+typedef struct focus_optim_hyper {
+    double beta1, beta2;            /* ADAM, ADAMW */
+    double momentum, dampening;     /* SGD */
+    float eps, max_norm, clip_value;
+    int32_t nesterov, write_clipped_grads, pad_;
+} focus_optim_hyper;
+int focus_optim_step(int mode, const focus_adamw_item* items, float* const* grads, int n_items, int n_units, const float* groups,
+                     float* steps, void* workspace, size_t workspace_bytes, float* total_norm, const focus_optim_hyper* hyper,
+                     void* stream);
+
 /* OCP FP8 E4M3 working copies of fp32 master weights with one scale per tensor (BASELINE configs[4]; the reference's
  * EK_ORVIT_MF_HR.yaml trains fp16-autocast: these replace autocast's per-use fp16 weight casts, train_net.py:84):
  * scale = amax|w| / 448, dst[r,c] = e4m3(w[r,c] / scale) (row-major, optional), dstT[c,r] = the same code transposed
