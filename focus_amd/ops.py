@@ -3059,3 +3059,125 @@ def soft_target_ce(logits, target, reduction="mean"):
                          (tuple(logits.shape), tuple(target.shape)))
     _dt(logits)
     return _XentSoftFn.apply(logits, target.detach().float().contiguous(), reduction == "mean")
+
+
+# --------------------------------------------------------------------------------------------------
+# RandAugment on device uint8 clips (randaug.hip; the plans come from slowfast/datasets/rand_augment.py)
+# --------------------------------------------------------------------------------------------------
+RANDAUG_OPS = ("copy", "autocontrast", "equalize", "invert", "posterize", "solarize", "solarize_add", "brightness", "color",
+               "contrast", "sharpness", "rotate", "shear_x", "shear_y", "translate_x", "translate_y")   # enum focus_randaug_op
+RANDAUG_STAT_OPS, RANDAUG_AFFINE_OPS = (1, 2, 9), (11, 12, 13, 14, 15)
+RANDAUG_STAT_WORDS = 776
+RANDAUG_RESAMPLES = (2, 3)                  # PIL's BILINEAR, BICUBIC
+
+
+def _randaug_item_dtype():
+    import numpy as np
+    return np.dtype([("src", "<u8"), ("dst", "<u8"), ("src_stride", "<i8"), ("dst_stride", "<i8"), ("stats_off", "<i8"),
+                     ("coef", "<f8", (6,)), ("farg", "<f4"), ("iarg", "<i4"), ("H", "<i4"), ("W", "<i4"), ("op", "<i4"),
+                     ("resample", "<i4"), ("fill", "u1", (4,)), ("pad_", "<i4")])          # focus_randaug_item, 120 bytes
+
+
+def _randaug_record(r, where):
+    """A layer record of a plan, validated -> (op, farg, iarg, fill, resample, coef); a closed gate or PIL's plain copy -> None."""
+    import math
+    import numpy as np
+    if r is None:
+        return None
+    op = r["op"]
+    if isinstance(op, bool) or not isinstance(op, (int, np.integer)) or not 0 <= int(op) < len(RANDAUG_OPS):
+        raise ValueError("focus_amd: %s: unknown RandAugment op %r" % (where, op))
+    op = int(op)
+    fill = tuple(int(v) for v in r.get("fill", (128, 128, 128)))
+    if len(fill) != 3 or any(not 0 <= v <= 255 for v in fill):
+        raise ValueError("focus_amd: %s: fill %r is not three bytes" % (where, fill))
+    rs, coef = 2, (0.0,) * 6
+    if op in RANDAUG_AFFINE_OPS:
+        rs = r.get("resample", 2)
+        rs = rs[0] if isinstance(rs, (tuple, list)) and len(rs) == 1 else rs
+        if rs not in RANDAUG_RESAMPLES:
+            raise ValueError("focus_amd: %s: resample %r (2 bilinear or 3 bicubic)" % (where, rs))
+        coef = r.get("coef")
+        if coef is None:                                              # PIL returns a copy (rotation by 0)
+            return None
+        if len(coef) != 6 or not all(math.isfinite(float(v)) for v in coef):
+            raise ValueError("focus_amd: %s: six finite coefficients, got %r" % (where, coef))
+        coef = tuple(float(v) for v in coef)
+    return op, float(r.get("farg", 0.0)), int(r.get("iarg", 0)), fill, int(rs), coef
+
+
+def randaug_apply(clips_u8, plans):
+    """RandAugment of a batch of decoded clips on the device.  clips_u8: uint8 CUDA tensors [T,H,W,3] with dense pixels (H, W,
+    T may differ per clip); plans[i][t]: the layer records of frame t of clip i, as RandAugment.plan returns them for one
+    image -- None (the gate stayed closed: the frame is copied) or a mapping with op (a code of RANDAUG_OPS), farg, iarg,
+    resample (2 bilinear / 3 bicubic, or a 1-tuple of it), coef (six floats; None: a plain copy) and fill.  Every frame has the
+    same number of layers.  Returns NEW tensors of the inputs' shapes; the inputs are not written.  One H2D copy of the
+    descriptor table of all layers, then per layer the apply launch and, when a frame of the layer needs its histogram or its
+    mean, a stats launch before it.  Everything the kernel cannot report is a ValueError here.  No CPU fallback."""
+    import numpy as np
+    t = randaug_table(clips_u8, plans)
+    rec, n, dev = t["rec"], t["rec"].shape[1], clips_u8[0].device
+    L = _lib.lib()
+    ws_bytes = int(L.focus_randaug_workspace_bytes(t["n_stats"]))
+    with torch.cuda.device(dev):
+        ws = torch.zeros(ws_bytes // 4, dtype=torch.int32, device=dev) if t["n_stats"] else None
+        items = torch.from_numpy(rec.reshape(-1).view(np.uint8)).pin_memory().to(dev, non_blocking=True)
+        for l in range(rec.shape[0]):
+            _lib.check(L.focus_randaug_layer(ctypes.c_void_p(items.data_ptr() + l * n * rec.dtype.itemsize), n, t["max_h"],
+                                             t["max_w"], int(t["need_stats"][l]), _p(ws), ws_bytes, _stream()), "randaug_layer")
+    return t["outs"]
+
+
+def randaug_table(clips_u8, plans):
+    """The host half of randaug_apply: validates, allocates the output and scratch clips and writes the focus_randaug_item
+    table of every layer.  -> dict(rec [depth, n] structured array, outs, scratch, n_stats, need_stats [depth], max_h, max_w)."""
+    import numpy as np
+    if not clips_u8 or len(clips_u8) != len(plans):
+        raise ValueError("focus_amd: randaug_apply takes one plan list per clip and at least one clip")
+    dev = clips_u8[0].device
+    depth = None
+    frames = []                                                       # (clip index, t, H, W, validated layers)
+    for i, (c, pl) in enumerate(zip(clips_u8, plans)):
+        if c.dtype != torch.uint8 or c.dim() != 4 or c.shape[3] != 3 or c.numel() == 0 or c.stride()[2:] != (3, 1):
+            raise ValueError("focus_amd: clip %d is not a non-empty uint8 [T,H,W,3] tensor with dense pixels" % i)
+        if c.device != dev:
+            raise ValueError("focus_amd: the clips of one launch live on one device")
+        if c.shape[1] > 32768 or c.shape[2] > 32768:
+            raise ValueError("focus_amd: clip %d: frames above 32768 pixels a side are not supported" % i)
+        if len(pl) != c.shape[0]:
+            raise ValueError("focus_amd: clip %d has %d frames and %d plans" % (i, c.shape[0], len(pl)))
+        for t, layers in enumerate(pl):
+            depth = len(layers) if depth is None else depth
+            if len(layers) != depth or depth < 1:
+                raise ValueError("focus_amd: every frame's plan has the same number of layers, at least one "
+                                 "(clip %d frame %d: %d, expected %d)" % (i, t, len(layers), depth))
+            frames.append((i, t, int(c.shape[1]), int(c.shape[2]),
+                           [_randaug_record(r, "clip %d frame %d layer %d" % (i, t, l)) for l, r in enumerate(layers)]))
+    n = len(frames)
+    if n > 65535:
+        raise ValueError("focus_amd: randaug_apply takes at most 65535 frames per call (got %d)" % n)
+    if not dev.type == "cuda":
+        raise ValueError("focus_amd: randaug_apply runs on the MI355X only (got %s tensors); there is no CPU fallback" % dev)
+    outs = [torch.empty(c.shape, dtype=torch.uint8, device=dev) for c in clips_u8]
+    scratch = [torch.empty_like(o) for o in outs] if depth > 1 else outs
+    rec = np.zeros((depth, n), dtype=_randaug_item_dtype())
+    n_stats, need_stats = 0, [False] * depth
+    for k, (i, t, H, W, layers) in enumerate(frames):
+        for l, r in enumerate(layers):
+            # layer l writes `outs` when an even number of layers follows it, so the last one always does
+            src = clips_u8[i] if l == 0 else (outs if (depth - l) % 2 == 0 else scratch)[i]
+            dst = (outs if (depth - 1 - l) % 2 == 0 else scratch)[i]
+            it = rec[l, k]
+            it["src"], it["src_stride"] = src.data_ptr() + t * src.stride(0), src.stride(1)
+            it["dst"], it["dst_stride"] = dst.data_ptr() + t * dst.stride(0), dst.stride(1)
+            it["H"], it["W"], it["stats_off"], it["op"], it["resample"] = H, W, -1, 0, 2
+            if r is None:
+                continue
+            it["op"], it["farg"], it["iarg"], it["resample"], it["coef"] = r[0], r[1], r[2], r[4], r[5]
+            it["fill"][:3] = r[3]
+            if r[0] in RANDAUG_STAT_OPS:
+                it["stats_off"] = n_stats * RANDAUG_STAT_WORDS
+                n_stats += 1
+                need_stats[l] = True
+    return dict(rec=rec, outs=outs, scratch=scratch, n_stats=n_stats, need_stats=need_stats,
+                max_h=max(f[2] for f in frames), max_w=max(f[3] for f in frames))

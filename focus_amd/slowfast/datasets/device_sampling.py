@@ -5,8 +5,9 @@ resize of the whole frame, a crop, a flip, the channel reversal.  All three of i
 random resized crop (the branch every shipped ORViT config takes: AUG.ENABLE with TRAIN_JITTER_SCALES_RELATIVE), the test
 views 0/1/2 -- resize a source rectangle to (rh, rw) and take a window of the result, so here the HOST only draws the
 reference's random numbers and moves the boxes (`sampling_params`, bit-identical to the reference) and ONE HIP launch
-produces the pixels of the whole batch (`ops.clip_sample`).  RandAugment, colour jitter and random erasing are not part of
-this path."""
+produces the pixels of the whole batch (`ops.clip_sample`).  RandAugment runs in front of it, on the uint8 clips and on the
+device too (`augment_clips`: the host draws the reference's numbers and moves the boxes, `ops.randaug_apply` runs the ops);
+colour jitter and random erasing are not part of this path."""
 import math
 
 import numpy as np
@@ -121,3 +122,41 @@ def sample_clips(cfg, clips_u8, boxes, spatial_idx=-1, min_scale=None, max_scale
                                  dtype, "BCTHW")
     # one hand-off for the batch: boxes_to_orvit_format works box by box, so this is what B calls would give
     return inputs, boxes_to_orvit_format(np.stack(out_boxes), crop_size, crop_size)
+
+
+def augment_clips(cfg, clips_u8, boxes=None):
+    """The device form of ssv2.py:361-393 (`_aug_frame` up to `_list_img_to_frames`): RandAugment of a batch of decoded clips
+    under cfg.AUG.  clips_u8: uint8 [T,H,W,3] CUDA tensors; boxes: None, or per clip a numpy [T,O,4] array of xyxy pixel
+    boxes.  Under AUG.DIFFERENT_AUG_PER_FRAME every frame gets a fresh transform and its own draws, as the reference builds
+    them; otherwise one transform plans the whole clip (with `interpolation: random` its frames still draw their resample one
+    by one).  The draws are the reference's, clip by clip and frame by frame in order; ONE ops.randaug_apply runs the batch.
+    Returns (clips_u8, boxes) for sample_clips: new tensors and new box arrays, or the inputs themselves when AUG.ENABLE is
+    false or AUG.AA_TYPE is empty.  AUG.RE_PROB and AUG.COLOR_JITTER are not read: they stay the reference's."""
+    aug = getattr(cfg, "AUG", None)
+    aa_type = getattr(aug, "AA_TYPE", "") if aug is not None else ""
+    if aug is None or not getattr(aug, "ENABLE", False) or not aa_type:
+        return clips_u8, boxes
+    if boxes is not None and len(boxes) != len(clips_u8):
+        raise ValueError("augment_clips takes one box array per clip")
+    interpolation = getattr(aug, "INTERPOLATION", "bicubic")
+    per_frame = bool(getattr(aug, "DIFFERENT_AUG_PER_FRAME", False))
+    plans, out_boxes = [], []
+    for i, clip in enumerate(clips_u8):
+        T, H, W = int(clip.shape[0]), int(clip.shape[1]), int(clip.shape[2])
+        b = None if boxes is None else np.asarray(boxes[i])
+        if b is not None and (b.ndim != 3 or b.shape[0] != T or b.shape[2] != 4):
+            raise ValueError("augment_clips: clip %d has %d frames and boxes of shape %s" % (i, T, b.shape))
+        make = lambda: transform.create_random_augment((H, W), aa_type, interpolation, with_boxes=b is not None)
+        if per_frame:
+            frames, moved = [], []
+            for t in range(T):
+                layers, bt = make().plan((W, H), None if b is None else b[[t]], 1)
+                frames.append(layers)
+                moved.append(bt)
+            b = None if b is None else np.concatenate(moved, axis=0)
+        else:
+            layers, b = make().plan((W, H), b, T)
+            frames = [[None if r is None else dict(r, resample=(r["resample"][t],)) for r in layers] for t in range(T)]
+        plans.append(frames)
+        out_boxes.append(b)
+    return ops.randaug_apply(clips_u8, plans), (None if boxes is None else out_boxes)

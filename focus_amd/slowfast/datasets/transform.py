@@ -167,3 +167,26 @@ def random_resized_crop(images, target_height, target_width, scale=(0.8, 1.0), r
     if boxes is not None:
         return ret, resized_crop_boxes(boxes, i, j, h, w, target_height, target_width)
     return ret
+
+
+def _pil_interp(method):
+    """transform.py:606-614: PIL's resample code of an interpolation name (bilinear when unknown)."""
+    return {"bicubic": 3, "lanczos": 1, "hamming": 5}.get(method, 2)
+
+
+def create_random_augment(input_size, auto_augment=None, interpolation="bilinear", with_boxes=False):
+    """transform.py:649-684 for device clips: the RandAugment planner of datasets/rand_augment.py for a policy string such as
+    "rand-m7-n4-mstd0.5-inc1".  The returned object takes no PIL images: `plan(size, boxes)` draws what the reference would
+    draw and `ops.randaug_apply` runs the result (datasets/device_sampling.augment_clips).  with_boxes selects the reference's
+    boxes variant, which differs in the draws by nothing; boxes are moved whenever plan() is given some."""
+    from .rand_augment import rand_augment_transform
+    img_size = input_size[-2:] if isinstance(input_size, tuple) else input_size
+    if auto_augment:
+        assert isinstance(auto_augment, str)
+        img_size_min = min(img_size) if isinstance(img_size, tuple) else img_size
+        aa_params = {"translate_const": int(img_size_min * 0.45)}
+        if interpolation and interpolation != "random":
+            aa_params["interpolation"] = _pil_interp(interpolation)
+        if auto_augment.startswith("rand"):
+            return rand_augment_transform(auto_augment, aa_params)
+    raise NotImplementedError

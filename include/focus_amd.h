@@ -758,6 +758,70 @@ int focus_mixup_target(const int64_t* labels, float* target, int B, int V, float
 int focus_xent_soft(const float* logits, const float* target, float* loss_rows, float* dlogits, int R, int V,
                     void* stream);
 
+/* -------------------------------------------------------------------------------------------------
+ * RandAugment on decoded uint8 frames (randaug.hip; datasets/rand_augment.py of the reference, which runs the ops through
+ * PIL on a loader worker).  The unit of work is one frame, uint8 [H][W][3] with a row stride in BYTES, and one op; one call
+ * runs one LAYER (one op slot of the policy) for every frame of a batch, each frame with its own op, size and buffers, in at
+ * most two launches: a stats launch (only when need_stats != 0) and the apply launch.  A policy of n layers is n calls that
+ * ping-pong between caller-owned buffers; src is never written.  The arithmetic is PIL's, bit for bit:
+ *
+ *   table ops   out = lut[c][in], a 256-entry table per channel built by every apply workgroup at its start.
+ *               INVERT 255-v;  POSTERIZE v & ~(2^(8-iarg)-1) (iarg >= 8: identity);  SOLARIZE v < iarg ? v : 255-v;
+ *               SOLARIZE_ADD v < 128 ? min(255, v+iarg) : v;  BRIGHTNESS blend(0, v, farg);
+ *               AUTOCONTRAST (cutoff 0): lo / hi = first / last occupied bin of the channel's histogram; hi <= lo: identity;
+ *                 else scale = 255.0/(hi-lo), offset = -lo*scale (fp64), lut = clamp((int)(v*scale + offset), 0, 255);
+ *               EQUALIZE: step = (sum(h) - h[last occupied]) / 255 (integers); fewer than two occupied bins or step == 0:
+ *                 identity; else lut[v] = min(255, (step/2 + sum(h[0..v-1])) / step).
+ *   blend ops   blend(d, v, f) = clamp-then-truncate of  fp32(d) + f * fp32(v - d),  the product and the sum rounded
+ *               separately (never an fma).  COLOR d = L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16;  CONTRAST d =
+ *               (int)(mean(L) + 0.5), the mean in fp64 from the stats launch;  SHARPNESS d = the 3x3 SMOOTH filter
+ *               (1 1 1 / 1 5 1 / 1 1 1) / 13 in fp32, accumulated from 0.5 row by row (y+1, y, y-1), border pixels copied.
+ *   affine ops  ROTATE, SHEAR_X, SHEAR_Y, TRANSLATE_X, TRANSLATE_Y are one kernel path: for output pixel (x, y)
+ *               xs = coef[0]*(x+0.5) + coef[1]*(y+0.5) + coef[2],  ys = coef[3]*(x+0.5) + coef[4]*(y+0.5) + coef[5]  (fp64);
+ *               the pixel is `fill` exactly when xs < 0, xs >= W, ys < 0 or ys >= H; else it is resampled at (xs-0.5, ys-0.5)
+ *               with PIL's bilinear (resample 2) or bicubic (resample 3, a = -0.5) filter in fp64, neighbours clamped to the
+ *               frame, truncated (bicubic: clamped first).  The host computes the coefficients: no trigonometry here.
+ *   COPY        out = in (a frame whose draw left it unchanged).
+ *
+ * Stats: FOCUS_RANDAUG_STAT_WORDS 32-bit words per frame that asks for them (stats_off >= 0, an offset in WORDS into the
+ * workspace, even): words [0,768) the histograms h[c][v], words 768-769 the 64-bit sum of L.  LDS histograms per workgroup
+ * are merged with vector atomics, so the CALLER ZEROES the words of a frame before the call; integer sums are the same in
+ * any order.  AUTOCONTRAST, EQUALIZE and CONTRAST need a slot (stats_off >= 0; without one the frame is copied) and
+ * need_stats != 0 (with need_stats == 0 and a workspace, the slot is read as the caller left it).
+ *
+ * `items`: DEVICE array of n_items descriptors, owned by the caller.  This entry point cannot read it: the caller guarantees
+ * valid pointers and strides, H <= max_h, W <= max_w (a larger frame is skipped), op and resample codes from the lists
+ * below (an unknown op copies, an unknown resample is bilinear) and stats_off + FOCUS_RANDAUG_STAT_WORDS within the
+ * workspace (a slot outside workspace_bytes is ignored and its frame copied).  focus_amd.ops.randaug_apply validates all of
+ * it.  No allocation, no synchronisation, no host round trip.
+ *
+ * Status, in this order, before any launch: FOCUS_ERR_NULL (items; workspace when need_stats); FOCUS_OK without a launch
+ * for n_items <= 0; FOCUS_ERR_SHAPE (max_h or max_w outside [1, 32768], n_items > 65535); FOCUS_ERR_ALIGN (workspace not
+ * 8-byte aligned); FOCUS_ERR_WORKSPACE (need_stats and workspace_bytes < focus_randaug_workspace_bytes(1)).
+ * ----------------------------------------------------------------------------------------------*/
+#define FOCUS_RANDAUG_STAT_WORDS 776
+enum focus_randaug_op {
+    FOCUS_RA_COPY = 0, FOCUS_RA_AUTOCONTRAST = 1, FOCUS_RA_EQUALIZE = 2, FOCUS_RA_INVERT = 3, FOCUS_RA_POSTERIZE = 4,
+    FOCUS_RA_SOLARIZE = 5, FOCUS_RA_SOLARIZE_ADD = 6, FOCUS_RA_BRIGHTNESS = 7, FOCUS_RA_COLOR = 8, FOCUS_RA_CONTRAST = 9,
+    FOCUS_RA_SHARPNESS = 10, FOCUS_RA_ROTATE = 11, FOCUS_RA_SHEAR_X = 12, FOCUS_RA_SHEAR_Y = 13, FOCUS_RA_TRANSLATE_X = 14,
+    FOCUS_RA_TRANSLATE_Y = 15
+};
+#define FOCUS_RA_BILINEAR 2 /* PIL's codes */
+#define FOCUS_RA_BICUBIC 3
+typedef struct focus_randaug_item {
+    const uint8_t* src;
+    uint8_t* dst;
+    int64_t src_stride, dst_stride, stats_off;
+    double coef[6];
+    float farg;
+    int32_t iarg, H, W, op, resample;
+    uint8_t fill[4];
+    int32_t pad_;
+} focus_randaug_item;
+size_t focus_randaug_workspace_bytes(int n_stats_frames);
+int focus_randaug_layer(const focus_randaug_item* items, int n_items, int max_h, int max_w, int need_stats,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
