@@ -3181,3 +3181,79 @@ def randaug_table(clips_u8, plans):
                 need_stats[l] = True
     return dict(rec=rec, outs=outs, scratch=scratch, n_stats=n_stats, need_stats=need_stats,
                 max_h=max(f[2] for f in frames), max_w=max(f[3] for f in frames))
+
+
+# --------------------------------------------------------------------------------------------------
+# Slot masks -> segments, ORViT boxes and FG-ARI tables (csrc/slot_segments.hip)
+# --------------------------------------------------------------------------------------------------
+def _need_contiguous(t, what):
+    if not t.is_contiguous():
+        raise ValueError("focus_amd: %s must be contiguous; got strides %s for shape %s" % (
+            what, tuple(t.stride()), tuple(t.shape)))
+
+
+def slot_segments(attn, He, We):
+    """attn [B,T,N = He*We,K] (the slot update's attention, fp32 or bf16, contiguous) -> (seg uint8 [B,T,N], the arg-max
+    slot of each cell with ties to the lowest index; stats int32 [B,T,K,5] = (count, xmin, ymin, xmax, ymax) per frame and
+    slot in cell units, (0, We, He, -1, -1) for a slot without a cell).  No CPU fallback."""
+    _need_gpu(attn)
+    He, We = int(He), int(We)
+    if attn.dim() != 4 or attn.shape[2] != He * We or not 1 <= attn.shape[3] <= 32 or He < 1 or We < 1:
+        raise ValueError("focus_amd: slot_segments takes attn [B,T,He*We,K] with 1 <= K <= 32; got %s for a %dx%d grid" % (
+            tuple(attn.shape), He, We))
+    _need_contiguous(attn, "slot_segments' attn")
+    B, T, N, K = attn.shape
+    seg = torch.empty(B, T, N, device=attn.device, dtype=torch.uint8)
+    stats = torch.empty(B, T, K, 5, device=attn.device, dtype=torch.int32)
+    with torch.cuda.device(attn.device):
+        _lib.check(_lib.lib().focus_slot_segments(_p(attn), _dt(attn), B, T, He, We, K, _p(seg), _p(stats), _stream()),
+                   "slot_segments")
+    return seg, stats
+
+
+def slot_boxes(stats, He, We, H, W, O, drop_largest=True):
+    """stats [B,T,K,5] of slot_segments -> (boxes fp32 [B,T,O,4] in the orvit_bboxes encoding, slot_ids int32 [B,O]): per
+    clip the O largest slots (after dropping the largest = background when drop_largest), in ascending slot index; missing
+    objects are zero rows with id -1.  (H, W) is the frame the boxes refer to; He | H and We | W."""
+    _need_gpu(stats)
+    He, We, H, W, O = int(He), int(We), int(H), int(W), int(O)
+    if stats.dim() != 4 or stats.shape[3] != 5 or stats.dtype != torch.int32 or not 1 <= stats.shape[2] <= 32 or O < 0:
+        raise ValueError("focus_amd: slot_boxes takes int32 stats [B,T,K,5] with 1 <= K <= 32 and O >= 0; got %s %s" % (
+            stats.dtype, tuple(stats.shape)))
+    if He < 1 or We < 1 or H < 1 or W < 1 or H % He or W % We:
+        raise ValueError("focus_amd: slot_boxes: the %dx%d slot grid does not divide the %dx%d frame" % (He, We, H, W))
+    _need_contiguous(stats, "slot_boxes' stats")
+    B, T, K, _ = stats.shape
+    boxes = torch.empty(B, T, O, 4, device=stats.device, dtype=torch.float32)
+    slot_ids = torch.empty(B, O, device=stats.device, dtype=torch.int32)
+    with torch.cuda.device(stats.device):
+        _lib.check(_lib.lib().focus_slot_boxes(_p(stats), B, T, K, He, We, H, W, O, int(bool(drop_largest)), _p(boxes),
+                                               _p(slot_ids), _stream()), "slot_boxes")
+    return boxes, slot_ids
+
+
+def seg_contingency(seg, truth, He, We, K, first_segment=1):
+    """seg uint8 [B,T,He*We] (or [B,T,He,We]) and truth [B,T,S,1,H,W] (bool / uint8 / fp32, non-zero = member) -> the FG-ARI
+    contingency tables int32 [B, S - first_segment, K]: pixels of truth segment s (all frames) whose cell belongs to slot k."""
+    _need_gpu(seg, truth)
+    He, We, K, first_segment = int(He), int(We), int(K), int(first_segment)
+    if truth.dtype == torch.bool:
+        truth = truth.view(torch.uint8)
+    if seg.dtype != torch.uint8 or truth.dtype not in (torch.uint8, torch.float32):
+        raise ValueError("focus_amd: seg_contingency takes a uint8 seg and a bool, uint8 or float32 truth; got %s, %s" % (
+            seg.dtype, truth.dtype))
+    if truth.dim() != 6 or truth.shape[3] != 1 or seg.dim() not in (3, 4) or seg.shape[:2] != truth.shape[:2] \
+            or seg.numel() != truth.shape[0] * truth.shape[1] * He * We or seg.device != truth.device:
+        raise ValueError("focus_amd: seg_contingency takes seg [B,T,He*We] and truth [B,T,S,1,H,W] on one device; got %s, %s"
+                         % (tuple(seg.shape), tuple(truth.shape)))
+    B, T, S, _, H, W = truth.shape
+    if not 1 <= K <= 32 or He < 1 or We < 1 or H % He or W % We or not 0 <= first_segment < S or T * H * W >= 2 ** 31:
+        raise ValueError("focus_amd: seg_contingency: K %d, grid %dx%d, frame %dx%d, S %d, first_segment %d" % (
+            K, He, We, H, W, S, first_segment))
+    _need_contiguous(seg, "seg_contingency's seg")
+    _need_contiguous(truth, "seg_contingency's truth")
+    table = torch.empty(B, S - first_segment, K, device=seg.device, dtype=torch.int32)
+    with torch.cuda.device(seg.device):
+        _lib.check(_lib.lib().focus_seg_contingency(_p(seg), _p(truth), int(truth.dtype == torch.float32), B, T, S, H, W, He, We,
+                                                    K, first_segment, _p(table), _stream()), "seg_contingency")
+    return table

@@ -421,6 +421,7 @@ class STEVE(nn.Module):
         self.image_size = args.SLOTS.IMG_SIZE
         self.vocab_size = args.SLOTS.VOCAB_SIZE
         self.d_model = args.SLOTS.DECODER.DIM
+        self.orvit_objects = int(args.ORVIT.O) if "ORVIT" in args else 5      # object_boxes' default O: what ORViT takes
         self.compute_dtype = torch.bfloat16 if args.TRAIN.MIXED_PRECISION else torch.float32
         # build-owned key: the slot update (SlotAttentionVideo, ~2000 small launches forward + backward) is captured once
         # into a pair of HIP graphs (torch.cuda.make_graphed_callables) and replayed inside the eager training step
@@ -479,7 +480,8 @@ class STEVE(nn.Module):
         return flat.contiguous(memory_format=torch.channels_last) if self.channels_last else flat
 
     # ---- shared by forward / encode (steve.py:294-313, :333-353) ----
-    def _slots(self, video, noise=None):
+    def _slot_attns(self, video, noise=None):
+        """The encoder up to the slot update: (slots [B,T,K,Ds], attns [B,T,N,K] as the update leaves them, H_enc, W_enc)."""
         B, T, C, H, W = video.shape
         enc = self.steve_encoder
         emb = enc.pos(self._conv(enc.cnn, self._frames(video)))                                       # B*T, d_model, H_enc, W_enc
@@ -493,6 +495,11 @@ class STEVE(nn.Module):
             slots, attns = self._savi_graphed(emb_set, noise)
         else:
             slots, attns = enc.savi(emb_set, noise=noise)                                 # [B,T,K,Ds], [B,T,N,K]
+        return slots, attns, H_enc, W_enc
+
+    def _slots(self, video, noise=None):
+        B, T, C, H, W = video.shape
+        slots, attns, H_enc, W_enc = self._slot_attns(video, noise)
         attns = attns.float().transpose(-1, -2).reshape(B, T, self.num_slots, 1, H_enc, W_enc) \
             .repeat_interleave(H // H_enc, dim=-2).repeat_interleave(W // W_enc, dim=-1)  # B, T, K, 1, H, W
         return slots, attns
@@ -577,6 +584,27 @@ class STEVE(nn.Module):
         slots, attns = self._slots(video)
         attns_vis = video.unsqueeze(2) * attns + (1.0 - attns)
         return slots, attns_vis, attns
+
+    def segment(self, video):
+        """The hard masks of encode() at the slot grid's resolution, without the upsampled [B,T,K,1,H,W] tensor and
+        attns_vis: (slots [B,T,K,Ds], seg uint8 [B,T,H_enc,W_enc] = the arg-max slot of every cell, lowest index among equal
+        scores, stats int32 [B,T,K,5] = (count, xmin, ymin, xmax, ymax) per frame and slot in cells).  Nearest upsampling
+        repeats cells, so seg[..., y // sy, x // sx] is the arg-max of encode()'s masks at pixel (y, x).  Same encoder pass
+        and the same draw of the slot initialisation as encode()."""
+        B, T = video.shape[:2]
+        slots, attns, H_enc, W_enc = self._slot_attns(video)
+        seg, stats = ops.slot_segments(attns.contiguous(), H_enc, W_enc)
+        return slots, seg.view(B, T, H_enc, W_enc), stats
+
+    def object_boxes(self, video, num_objects=None, drop_largest=True):
+        """STEVE's objects as ORViT takes them: (boxes fp32 [B,T,O,4] = meta['orvit_bboxes'] for the video's H x W frame,
+        slot_ids int32 [B,O]), on the device.  Per clip the O slots of the largest area are kept (O = cfg.ORVIT.O by
+        default), after the largest one -- the background -- is dropped when drop_largest; object o is the same slot in every
+        frame, objects are ordered by slot index, missing ones are zero rows with slot id -1."""
+        H, W = video.shape[-2:]
+        O = self.orvit_objects if num_objects is None else int(num_objects)
+        _, seg, stats = self.segment(video)
+        return ops.slot_boxes(stats, seg.shape[2], seg.shape[3], H, W, O, drop_largest)
 
     def decode(self, slots):
         """steve.py:359-381: greedy autoregressive token generation, then the dVAE decoder.  In eval mode on the GPU the

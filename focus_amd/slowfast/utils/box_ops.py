@@ -1,4 +1,4 @@
-"""Box helpers on the hot path and on the data hand-off (mirror of slowfast/utils/box_ops.py:10-28, 108-131)."""
+"""Box helpers on the hot path and on the data hand-off (mirror of slowfast/utils/box_ops.py:10-28, 72-96, 108-131)."""
 import torch
 
 
@@ -15,6 +15,23 @@ def box_cxcywh_to_xyxy(x):
 def box_xyxy_to_cxcywh(x):
     x0, y0, x1, y1 = x.unbind(-1)
     return torch.stack([(x0 + x1) / 2, (y0 + y1) / 2, (x1 - x0), (y1 - y0)], dim=-1)
+
+
+def masks_to_boxes(masks):
+    """box_ops.py:72-96: masks [N,H,W] (0/1) -> the boxes around them, [N,4] xyxy in fp32 pixel coordinates (the last
+    column and row INSIDE the mask, not one past it).  An empty mask gives (1e8, 1e8, 0, 0), like the reference."""
+    if masks.numel() == 0:
+        return torch.zeros((0, 4), device=masks.device)
+    h, w = masks.shape[-2:]
+    y = torch.arange(0, h, dtype=torch.float, device=masks.device).view(1, h, 1)
+    x = torch.arange(0, w, dtype=torch.float, device=masks.device).view(1, 1, w)
+    inside = masks.bool()
+    x_mask, y_mask = masks * x, masks * y
+    x_max = x_mask.flatten(1).max(-1)[0]
+    x_min = x_mask.masked_fill(~inside, 1e8).flatten(1).min(-1)[0]
+    y_max = y_mask.flatten(1).max(-1)[0]
+    y_min = y_mask.masked_fill(~inside, 1e8).flatten(1).min(-1)[0]
+    return torch.stack([x_min, y_min, x_max, y_max], 1)
 
 
 def zero_empty_boxes(boxes, mode="cxcywh", eps=0.05):

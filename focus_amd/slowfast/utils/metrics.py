@@ -33,6 +33,18 @@ def evaluate_ari(true_mask, pred_mask):
     return float(ari_from_tables(table).sum() / B)
 
 
+def evaluate_ari_segments(truth, seg, num_slots, first_segment=1):
+    """evaluate_ari for hard masks kept at the slot grid's resolution.  truth [B,T,S,1,H,W] as the evaluation loader gives
+    it (non-zero = member; segments below first_segment, the background, are left out), seg uint8 [B,T,He,We] of
+    STEVE.segment.  The contingency tables are counted by focus_amd.ops.seg_contingency straight from the two -- the
+    integers evaluate_ari's one-hot matmul produces from the upsampled masks -- and go through ari_from_tables.  Returns the
+    batch mean as a Python float."""
+    from focus_amd import ops
+    He, We = seg.shape[-2:]
+    table = ops.seg_contingency(seg.contiguous(), truth.to(seg.device).contiguous(), He, We, num_slots, first_segment)
+    return float(ari_from_tables(table).sum() / table.shape[0])
+
+
 def topks_correct(preds, labels, ks):
     """metrics.py:107-138: number of samples whose label is among the k highest scores, for every k in ks."""
     assert preds.size(0) == labels.size(0), "Batch dim of predictions and labels must match"

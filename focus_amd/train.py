@@ -7,6 +7,8 @@ Differences that follow from the MI355X design and are deliberate:
   * the per-scalar blocking metric all-reduces (train_net.py:247-250) are packed into one collective
     (focus_amd/slowfast/utils/distributed.py:all_reduce).
 """
+import os
+
 import torch
 
 from .slowfast.utils import misc
@@ -158,13 +160,28 @@ def slot_eval_epoch(eval_loader, model, cfg=None):
     """FG-ARI evaluation of STEVE (tools/steve_eval_net.py:75-132): `eval_loader` yields (video [B,T,C,H,W], true_masks
     [B,T,S,1,H,W] with segment 0 = background); the slots' attention masks of `model.encode` are scored against the
     foreground segments over the whole clip (pixels of all frames flattened together).  Returns (mean, std over batches)
-    of 100 x ARI; the ARI itself is computed on the device (utils/metrics.evaluate_ari)."""
+    of 100 x ARI; the ARI itself is computed on the device (utils/metrics.evaluate_ari).
+    On the GPU, with a model that has `segment`, the masks stay at the slot grid's resolution: model.segment's arg-max map
+    and the truth go straight into the contingency tables (metrics.evaluate_ari_segments) -- the same integers, hence the
+    same scores, without the upsampled masks, attns_vis and the float64 one-hot.  FOCUS_SLOT_EVAL_FUSED=0 keeps the
+    encode + evaluate_ari path everywhere."""
     from .slowfast.utils import metrics
     model.eval()
     dev = next(model.parameters()).device
+    fused = dev.type == "cuda" and hasattr(model, "segment") and os.environ.get("FOCUS_SLOT_EVAL_FUSED", "1") != "0"
     scores = []
     for video, true_masks in eval_loader:
         video = video.to(dev)
+        if fused:
+            state = torch.cuda.get_rng_state(dev)
+            _, seg, _ = model.segment(video)                                              # [B,T,He,We]
+            if video.shape[-2] % seg.shape[-2] == 0 and video.shape[-1] % seg.shape[-1] == 0:
+                truth = true_masks.to(dev)
+                if truth.dtype not in (torch.bool, torch.uint8):
+                    truth = truth.to(torch.uint8)                                         # evaluate_ari's reading of the masks
+                scores.append(100 * metrics.evaluate_ari_segments(truth, seg, model.num_slots))
+                continue
+            torch.cuda.set_rng_state(state, dev)                 # a slot grid that does not divide the frame: the path below
         _, _, pred_masks = model.encode(video)                                            # [B,T,K,1,H,W]
         scores.append(100 * metrics.evaluate_ari(true_masks.to(dev).permute(0, 2, 1, 3, 4, 5)[:, 1:].flatten(start_dim=2),
                                                  pred_masks.permute(0, 2, 1, 3, 4, 5).flatten(start_dim=2)))

@@ -822,6 +822,50 @@ size_t focus_randaug_workspace_bytes(int n_stats_frames);
 int focus_randaug_layer(const focus_randaug_item* items, int n_items, int max_h, int max_w, int need_stats,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* -------------------------------------------------------------------------------------------------
+ * Slot masks -> segments, ORViT boxes and FG-ARI tables (slot_segments.hip): the hand-off from STEVE's slot attention
+ * (steve.py:333-353 of the reference, whose masks leave the model upsampled to the frame) to meta['orvit_bboxes'] and to
+ * the FG-ARI evaluation (utils/metrics.py:39-83), at the resolution of the slot grid.  Every result is an integer, or an
+ * fp32 value rounded once per step of the host chain it restates: results are the same bits on every run.
+ *
+ * focus_slot_segments: attn [B,T,N = He We,K] contiguous, fp32 or bf16, K innermost (the slot update's layout; rows need no
+ *   alignment beyond the element's) ->
+ *     seg   uint8 [B,T,N]    the arg-max slot of each cell, the LOWEST index among equal maxima (NaN scores: unspecified);
+ *     stats int32 [B,T,K,5]  (count, xmin, ymin, xmax, ymax) of each slot in each frame in cell units, cell n at
+ *                            y = n / We, x = n % We; a slot without a cell in the frame: (0, We, He, -1, -1).
+ *   attn is read once.  A frame split over several workgroups is combined by integer add / min / max atomics into stats
+ *   that a first launch set to the empty value.  Status, in this order: FOCUS_ERR_NULL; FOCUS_ERR_SHAPE (B or T < 0, K < 1,
+ *   K > 32, He < 1, We < 1, He We K >= 2^31); FOCUS_ERR_DTYPE; FOCUS_ERR_ALIGN (attn not element-aligned, stats not 4-byte
+ *   aligned); FOCUS_OK without a launch for B T == 0.
+ *
+ * focus_slot_boxes: stats -> boxes fp32 [B,T,O,4] in the orvit_bboxes encoding (cx, cy, w, h in [0,1]; all-zero row = no
+ *   object) and slot_ids int32 [B,O], one launch.  Per clip: area[k] = sum_t count[b,t,k]; with drop_largest the slot of
+ *   the largest area (ties: lowest index; the background) is removed; of the others with area > 0 the O largest are kept
+ *   (ties: lowest index) and written in ASCENDING SLOT INDEX, so object o is one slot in every frame; objects beyond the
+ *   kept ones are zero rows with slot_ids = -1.  With sx = W / We, sy = H / He (both must divide), the box of a kept slot
+ *   in a frame is the pixel box (xmin sx, ymin sy, xmax sx + sx - 1, ymax sy + sy - 1) in fp32 -- masks_to_boxes
+ *   (utils/box_ops.py:72-96) of the nearest-upsampled mask -- put through datasets/utils.boxes_to_orvit_format: IEEE
+ *   division by W or H, clip to [0,1], cx = (x0+x1)/2, cy = (y0+y1)/2, w = x1-x0, h = y1-y0, a zero row when w <= 0.05 or
+ *   h <= 0.05.  A slot without a cell in a frame gives a zero row there (masks_to_boxes itself returns (1e8, 1e8, 0, 0)).
+ *   Status: FOCUS_ERR_NULL; FOCUS_ERR_SHAPE (B, T or O < 0, K < 1, K > 32, He, We, H or W < 1, H % He or W % We != 0,
+ *   T He We >= 2^31, H or W > 2^24); FOCUS_ERR_ALIGN (4 bytes); FOCUS_OK without a launch for B == 0 or O == 0.
+ *
+ * focus_seg_contingency: seg uint8 [B,T,He We] and truth [B,T,S,1,H,W] (uint8 / bool, or fp32 when truth_is_f32; non-zero =
+ *   member, masks may overlap) -> table int32 [B, S - first_segment, K],
+ *     table[b,s,k] = #{(t,y,x): truth[b,t,s+first_segment,y,x] != 0 and seg[b,t,(y/sy) We + x/sx] == k}.
+ *   The table is zeroed on the stream first: the call leaves exactly these counts.  Truth is read once, 16 bytes per lane
+ *   when W allows it; counts are summed per wave in LDS, then one integer atomic per non-zero bin per workgroup.  A seg
+ *   value >= K counts nowhere.  Status: FOCUS_ERR_NULL; FOCUS_ERR_SHAPE (B or T < 0, S, H, W, He, We or K < 1, K > 32,
+ *   first_segment < 0, S - first_segment < 1, H % He or W % We != 0, T H W >= 2^31, B (S - first_segment) >= 2^26);
+ *   FOCUS_ERR_ALIGN (table or fp32 truth not 4-byte aligned); FOCUS_OK without a launch for B == 0.
+ * ----------------------------------------------------------------------------------------------*/
+int focus_slot_segments(const void* attn, int dtype, int B, int T, int He, int We, int K, uint8_t* seg, int32_t* stats,
+                        void* stream);
+int focus_slot_boxes(const int32_t* stats, int B, int T, int K, int He, int We, int H, int W, int O, int drop_largest,
+                     float* boxes, int32_t* slot_ids, void* stream);
+int focus_seg_contingency(const uint8_t* seg, const void* truth, int truth_is_f32, int B, int T, int S, int H, int W, int He,
+                          int We, int K, int first_segment, int32_t* table, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
