@@ -3257,3 +3257,112 @@ def seg_contingency(seg, truth, He, We, K, first_segment=1):
         _lib.check(_lib.lib().focus_seg_contingency(_p(seg), _p(truth), int(truth.dtype == torch.float32), B, T, S, H, W, He, We,
                                                     K, first_segment, _p(table), _stream()), "seg_contingency")
     return table
+
+
+# --------------------------------------------------------------------------------------------------
+# Step and test statistics (csrc/step_stats.hip)
+# --------------------------------------------------------------------------------------------------
+STATS_INTS, STATS_FLOATS = 16, 8      # the two accumulator tables of focus_topk_stats (include/focus_amd.h)
+
+
+def _stats_head(h, logits, labels, dense, B):
+    if logits.dim() != 2 or logits.dtype not in (torch.float32, torch.bfloat16) or logits.stride(1) != 1:
+        raise ValueError("focus_amd: topk_stats takes float32 or bfloat16 logits [B,V] with unit column stride; head %d is %s %s "
+                         "with strides %s" % (h, logits.dtype, tuple(logits.shape), tuple(logits.stride())))
+    if logits.shape[0] != B or labels.device != logits.device:
+        raise ValueError("focus_amd: topk_stats: head %d has logits %s on %s and labels %s on %s for a batch of %d" % (
+            h, tuple(logits.shape), logits.device, tuple(labels.shape), labels.device, B))
+    V = logits.shape[1]
+    if dense:
+        if labels.dtype != torch.float32 or tuple(labels.shape) != (B, V) or labels.stride(1) != 1 or V < 2:
+            raise ValueError("focus_amd: topk_stats: dense labels are float32 [B,V] like the logits, V >= 2; head %d has %s %s "
+                             "against logits %s" % (h, labels.dtype, tuple(labels.shape), tuple(logits.shape)))
+        ldl = labels.stride(0) if B > 1 else V
+    else:
+        if labels.dtype != torch.int64 or tuple(labels.shape) != (B,) or not labels.is_contiguous():
+            raise ValueError("focus_amd: topk_stats: class labels are contiguous int64 [B]; head %d has %s %s for a batch of %d" % (
+                h, labels.dtype, tuple(labels.shape), B))
+        ldl = 0
+    return [_p(logits), _dt(logits), V, logits.stride(0) if B > 1 else V, _p(labels), ldl]
+
+
+def topk_stats(acc_i, acc_f, preds=(), labels=(), ks=(1, 5), losses=(), batch=None):
+    """Adds one batch into the accumulator (acc_i int64 [16], acc_f float64 [8], see include/focus_amd.h): top-k correct counts
+    of up to two heads under the order "NaN greatest, ties to the lowest index", the count of rows correct in every head,
+    steps, samples, the double sums of up to three 0-d fp32 device losses, and the first step whose losses[0] is NaN.
+    preds: a tensor [B,V] or a tuple of one or two (fp32 / bf16; a row stride is passed as it is, nothing is copied);
+    labels: per head int64 [B] or dense float32 [B,V] (mixup targets, collapsed inside the kernel).  No heads (STEVE): give
+    `batch`.  One launch, no sync, no CPU fallback."""
+    preds = (preds,) if isinstance(preds, torch.Tensor) else tuple(preds)
+    labels = (labels,) if isinstance(labels, torch.Tensor) else tuple(labels)
+    losses = tuple(losses)
+    _need_gpu(acc_i, acc_f, *preds, *labels, *losses)
+    if acc_i.dtype != torch.int64 or acc_f.dtype != torch.float64 or acc_i.numel() != STATS_INTS or acc_f.numel() != STATS_FLOATS \
+            or not acc_i.is_contiguous() or not acc_f.is_contiguous():
+        raise ValueError("focus_amd: topk_stats takes accumulators int64 [%d] and float64 [%d]; got %s %s, %s %s" % (
+            STATS_INTS, STATS_FLOATS, acc_i.dtype, tuple(acc_i.shape), acc_f.dtype, tuple(acc_f.shape)))
+    heads = len(preds)
+    if heads > 2 or len(labels) != heads or len(losses) > 3:
+        raise ValueError("focus_amd: topk_stats takes at most two heads with one label tensor each and at most three losses; got "
+                         "%d heads, %d label tensors, %d losses" % (heads, len(labels), len(losses)))
+    for l in losses:
+        if l is not None and (l.dtype != torch.float32 or l.numel() != 1):
+            raise ValueError("focus_amd: topk_stats takes float32 scalar losses; got %s %s" % (l.dtype, tuple(l.shape)))
+    ks = tuple(int(k) for k in ks)
+    dense = 0
+    if heads:
+        B = preds[0].shape[0]
+        dense = int(labels[0].is_floating_point())
+        if any(int(l.is_floating_point()) != dense for l in labels):
+            raise ValueError("focus_amd: topk_stats: the heads' labels are either all class indices or all dense rows")
+        head_args = sum((_stats_head(h, p, l, dense, B) for h, (p, l) in enumerate(zip(preds, labels))), [])
+        head_args += [None, F32, 0, 0, None, 0] * (2 - heads)
+        vmin = min(p.shape[1] for p in preds)
+        if not 1 <= len(ks) <= 4 or ks[0] < 1 or any(b <= a for a, b in zip(ks, ks[1:])) or ks[-1] > vmin:
+            raise ValueError("focus_amd: topk_stats takes 1 to 4 ascending ks between 1 and the smallest class count %d; got %s" % (
+                vmin, ks))
+    else:
+        if batch is None:
+            raise ValueError("focus_amd: topk_stats without heads needs the batch size")
+        B = int(batch)
+        head_args = [None, F32, 0, 0, None, 0] * 2
+        ks = ks[:4]
+    k4 = list(ks) + [0] * (4 - len(ks))
+    l3 = [_p(l) for l in losses] + [None] * (3 - len(losses))
+    with torch.cuda.device(acc_i.device):
+        _lib.check(_lib.lib().focus_topk_stats(heads, B, *head_args, dense, len(ks), *k4, *l3, _p(acc_i), _p(acc_f), _stream()),
+                   "topk_stats")
+
+
+VIEW_MODES = {"sum": 0, "max": 1}
+
+
+def view_accumulate(preds, clip_ids, labels, num_clips, video_preds, video_labels, clip_count, flag, mode="sum"):
+    """Multi-view ensembling of one head: row i of preds [n,C] (fp32 / bf16, a row stride is passed as it is) is folded into
+    row clip_ids[i] // num_clips of video_preds fp32 [num_videos,C], rows of one video in ascending row order; video_labels
+    and clip_count (int64 [num_videos]) follow; flag int32 [1] gets bit 0 for a clip contradicting its video's label and
+    bit 1 for a clip id out of range.  One launch, no sync, no CPU fallback."""
+    _need_gpu(preds, clip_ids, labels, video_preds, video_labels, clip_count, flag)
+    if mode not in VIEW_MODES:
+        raise ValueError("focus_amd: view_accumulate's mode is 'sum' or 'max'; got %r" % (mode,))
+    if preds.dim() != 2 or preds.dtype not in (torch.float32, torch.bfloat16) or preds.stride(1) != 1:
+        raise ValueError("focus_amd: view_accumulate takes float32 or bfloat16 preds [n,C] with unit column stride; got %s %s with "
+                         "strides %s" % (preds.dtype, tuple(preds.shape), tuple(preds.stride())))
+    n, C = preds.shape
+    for t, what in ((clip_ids, "clip_ids"), (labels, "labels")):
+        if t.dtype != torch.int64 or tuple(t.shape) != (n,) or not t.is_contiguous():
+            raise ValueError("focus_amd: view_accumulate takes contiguous int64 %s [%d]; got %s %s" % (what, n, t.dtype, tuple(t.shape)))
+    if video_preds.dim() != 2 or video_preds.shape[1] != C or video_preds.dtype != torch.float32 or not video_preds.is_contiguous():
+        raise ValueError("focus_amd: view_accumulate takes a contiguous float32 table [num_videos,%d]; got %s %s" % (
+            C, video_preds.dtype, tuple(video_preds.shape)))
+    NV = video_preds.shape[0]
+    for t, what in ((video_labels, "video_labels"), (clip_count, "clip_count")):
+        if t.dtype != torch.int64 or tuple(t.shape) != (NV,) or not t.is_contiguous():
+            raise ValueError("focus_amd: view_accumulate takes contiguous int64 %s [%d]; got %s %s" % (what, NV, t.dtype, tuple(t.shape)))
+    if flag.dtype != torch.int32 or flag.numel() != 1 or int(num_clips) < 1 or C < 1:
+        raise ValueError("focus_amd: view_accumulate takes an int32 flag of one element, num_clips >= 1 and C >= 1; got %s %s, %s, %d"
+                         % (flag.dtype, tuple(flag.shape), num_clips, C))
+    with torch.cuda.device(preds.device):
+        _lib.check(_lib.lib().focus_view_accumulate(_p(preds), _dt(preds), n, C, preds.stride(0) if n > 1 else C, _p(clip_ids),
+                                                    _p(labels), int(num_clips), NV, VIEW_MODES[mode], _p(video_preds),
+                                                    _p(video_labels), _p(clip_count), _p(flag), _stream()), "view_accumulate")

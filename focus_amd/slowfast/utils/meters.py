@@ -47,3 +47,218 @@ class TestMeter(object):
         for k, x in zip(ks, correct):
             self.stats["top{}_acc".format(k)] = "{:.{prec}f}".format(float(x / self.video_preds.size(0)) * 100.0, prec=2)
         return self.stats
+
+
+# ---- statistics kept on the device (csrc/step_stats.hip) --------------------------------------------------------------------
+_STEPS, _SAMPLES, _NAN, _NAN_STEP, _CORRECT = 0, 1, 2, 3, 4       # the int64 table of focus_topk_stats
+_NI, _NF = 16, 8
+
+
+def _distributed_world():
+    import torch.distributed as dist
+    return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+
+
+class StepStats(object):
+    """The per-step numbers of the training and validation loops (train_net.py:151-269, :372-467) -- top-k errors, or for
+    EPIC-Kitchens verb / noun / action accuracies, the losses, and the NaN guard of misc.check_nan_losses -- accumulated by
+    one kernel launch per step in two small device tables.  `update` never synchronises; `read` is the only sync: one
+    all-reduce when there are several ranks, one small device-to-host copy, the window's figures, and the raise the
+    reference makes in the step when a loss was NaN.  A window is what lies between two reads; every read also folds its
+    window into host-side epoch totals (`epoch_stats`).
+
+    ks=() keeps no top-k figures (STEVE: update(None, None, loss, (mse, cross_entropy), batch=B)); `aux_names` names the
+    means of the aux losses in the figures (default: verb_loss, noun_loss when multitask)."""
+
+    def __init__(self, device, ks=(1, 5), multitask=False, aux_names=None):
+        self.ks = tuple(int(k) for k in ks)
+        self.multitask = bool(multitask)
+        self.aux_names = tuple(aux_names) if aux_names is not None else (("verb_loss", "noun_loss") if multitask else ())
+        if len(self.ks) > 4 or len(self.aux_names) > 2:
+            raise ValueError("StepStats keeps at most 4 ks and 2 aux losses; got %s, %s" % (self.ks, self.aux_names))
+        self.acc_i = torch.zeros(_NI, dtype=torch.int64, device=device)
+        self.acc_f = torch.zeros(_NF, dtype=torch.float64, device=device)
+        self.reset_epoch()
+
+    def reset_epoch(self):
+        self._epoch = torch.zeros(_NI + _NF, dtype=torch.float64)
+        self._steps_read = 0                                    # this rank's steps of the windows read so far
+
+    def update(self, preds, labels, loss, aux_losses=(), batch=None):
+        """One launch, no sync.  preds / labels: tensors, or for EPIC-Kitchens the {'verb','noun'} dicts; labels are class
+        indices or the dense rows of mixup; loss and aux_losses are 0-d device tensors."""
+        from focus_amd import ops
+        if isinstance(labels, dict):
+            preds, labels = (preds["verb"], preds["noun"]), (labels["verb"], labels["noun"])
+        elif preds is None:
+            preds, labels = (), ()
+        losses = [l.detach().float().reshape(()) for l in (loss,) + tuple(aux_losses)]
+        ops.topk_stats(self.acc_i, self.acc_f, tuple(p.detach() for p in _as_tuple(preds)), _as_tuple(labels),
+                       self.ks or (1,), losses, batch=batch)
+
+    def _figures(self, t, weighted):
+        ints, fl = t[:_NI], t[_NI:]
+        samples, steps = float(ints[_SAMPLES]), float(ints[_STEPS])
+        out = {}
+        pct = (lambda c: 100.0 * c / samples) if samples else (lambda c: float("nan"))
+        for j, k in enumerate(self.ks):
+            c = [float(ints[_CORRECT + 4 * h + j]) for h in range(3)]
+            if self.multitask:
+                out["verb_top%d_acc" % k], out["noun_top%d_acc" % k], out["action_top%d_acc" % k] = pct(c[0]), pct(c[1]), pct(c[2])
+            else:
+                out["top%d_err" % k] = pct(samples - c[0])
+        den = samples if weighted else steps
+        for i, name in enumerate(("loss",) + self.aux_names):
+            out[name] = float(fl[(3 if weighted else 0) + i]) / den if den else float("nan")
+        out["samples"] = int(samples)
+        return out
+
+    def read(self, reset=True, reduce=True):
+        """The window's figures.  Plain: top{k}_err, loss; EK: verb_/noun_/action_top{k}_acc, verb_loss, noun_loss, loss; both:
+        samples (over all ranks) and steps.  Percentages are 100 * count / samples, losses the mean over steps (and ranks).
+        Raises RuntimeError("ERROR: Got NaN losses ...") when a NaN loss was latched on any rank; by then the failing
+        step's update has been applied, and the window is reset as asked."""
+        t = torch.cat([self.acc_i.double(), self.acc_f])                      # counts are far below 2^53: exact in double
+        world = _distributed_world() if reduce else 1
+        if world > 1:
+            import torch.distributed as dist
+            own = t[:_NAN_STEP + 1].clone()                                   # this rank's steps and NaN step
+            dist.all_reduce(t)                                                # sums; the NaN flag becomes a count of ranks
+            t = torch.cat([t, own])
+        t = t.cpu()                                                           # the one copy to the host
+        t, own = t[:_NI + _NF], t[_NI + _NF:] if world > 1 else t
+        if reset:
+            self.acc_i.zero_()
+            self.acc_f.zero_()
+        nan_here = own[_NAN] > 0
+        nan_step = self._steps_read + int(own[_NAN_STEP])
+        if reset:
+            self._steps_read += int(own[_STEPS])
+            self._epoch += t
+        if t[_NAN] > 0:
+            raise RuntimeError("ERROR: Got NaN losses (step %d)" % nan_step if nan_here else
+                               "ERROR: Got NaN losses (on another rank)")
+        out = self._figures(t, weighted=False)
+        out["steps"] = int(t[_STEPS]) // world
+        return out
+
+    def epoch_stats(self):
+        """The totals of the windows read (and reset) so far, the way TrainMeter / EPICTrainMeter.log_epoch_stats report them:
+        errors and accuracies from the counts, losses weighted by the batch size."""
+        out = self._figures(self._epoch, weighted=True)
+        out["steps"] = self._steps_read
+        return out
+
+
+def _as_tuple(x):
+    return (x,) if isinstance(x, torch.Tensor) else tuple(x)
+
+
+class DeviceTestMeter(object):
+    """TestMeter with its tables on the device: `update_stats` is one focus_view_accumulate launch and no sync (CPU clip_ids
+    and labels are copied non-blocking), `finalize_metrics` scores the table with focus_topk_stats.  The assertion
+    TestMeter makes per batch -- the clips of a video agree on its label -- is deferred to finalize_metrics."""
+
+    def __init__(self, num_videos, num_clips, num_cls, overall_iters, device, ensemble_method="sum"):
+        if ensemble_method not in ("sum", "max"):
+            raise NotImplementedError("Ensemble Method {} is not supported".format(ensemble_method))
+        self.num_clips = num_clips
+        self.overall_iters = overall_iters
+        self.ensemble_method = ensemble_method
+        self.device = torch.device(device)
+        self.video_preds = torch.zeros((num_videos, num_cls), device=self.device)
+        self.video_labels = torch.zeros((num_videos), device=self.device).long()
+        self.clip_count = torch.zeros((num_videos), device=self.device).long()
+        self.flag = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.stats = {}
+
+    def reset(self):
+        self.clip_count.zero_()
+        self.video_preds.zero_()
+        self.video_labels.zero_()
+        self.flag.zero_()
+
+    def update_stats(self, preds, labels, clip_ids):
+        from focus_amd import ops
+        labels = labels.detach().to(self.device, torch.int64, non_blocking=True).contiguous()
+        clip_ids = clip_ids.detach().to(self.device, torch.int64, non_blocking=True).contiguous()
+        ops.view_accumulate(preds.detach(), clip_ids, labels, self.num_clips, self.video_preds, self.video_labels,
+                            self.clip_count, self.flag, self.ensemble_method)
+
+    def _check_flag(self, flag):
+        assert not flag & 1, "clips of one video disagree on its label"
+        assert not flag & 2, "a clip id lies outside [0, num_videos * num_clips)"
+
+    def finalize_metrics(self, ks=(1, 5)):
+        from focus_amd import ops
+        acc_i = torch.zeros(_NI, dtype=torch.int64, device=self.device)
+        acc_f = torch.zeros(_NF, dtype=torch.float64, device=self.device)
+        ops.topk_stats(acc_i, acc_f, self.video_preds, self.video_labels, ks)
+        complete = (self.clip_count == self.num_clips).all().to(torch.int64).reshape(1)
+        t = torch.cat([acc_i, complete, self.flag.to(torch.int64)]).cpu()     # the one copy to the host
+        self._check_flag(int(t[_NI + 1]))
+        self.stats = {"split": "test_final", "complete": bool(t[_NI])}
+        n = self.video_preds.size(0)
+        for j, k in enumerate(ks):
+            x = torch.tensor(float(t[_CORRECT + j]))                           # the fp32 count metrics.topks_correct returns
+            self.stats["top{}_acc".format(k)] = "{:.{prec}f}".format(float(x / n) * 100.0, prec=2)
+        return self.stats
+
+
+class EPICTestMeter(object):
+    """meters.py:1134-1273 with the two tables on the device: two focus_view_accumulate launches per batch; the narration ids
+    stay on the host, indexed from the host clip_ids."""
+
+    def __init__(self, num_videos, num_clips, num_cls=(97, 300), overall_iters=0, device="cuda"):
+        import numpy as np
+        self.num_clips = num_clips
+        self.overall_iters = overall_iters
+        self.device = torch.device(device)
+        self.verb_video_preds = torch.zeros((num_videos, num_cls[0]), device=self.device)
+        self.noun_video_preds = torch.zeros((num_videos, num_cls[1]), device=self.device)
+        self.verb_video_labels = torch.zeros((num_videos), device=self.device).long()
+        self.noun_video_labels = torch.zeros((num_videos), device=self.device).long()
+        self.metadata = np.zeros(num_videos, dtype=object)
+        self.clip_count = torch.zeros((num_videos), device=self.device).long()
+        self._noun_count = torch.zeros((num_videos), device=self.device).long()
+        self.flag = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.stats = {}
+
+    def reset(self):
+        for t in (self.clip_count, self._noun_count, self.verb_video_preds, self.verb_video_labels, self.noun_video_preds,
+                  self.noun_video_labels, self.flag):
+            t.zero_()
+        self.metadata.fill(0)
+
+    def update_stats(self, preds, labels, metadata, clip_ids):
+        from focus_amd import ops
+        host_ids = clip_ids.detach().cpu() if not clip_ids.is_cuda else None
+        ids = clip_ids.detach().to(self.device, torch.int64, non_blocking=True).contiguous()
+        for p, l, table, tl, cnt in ((preds[0], labels[0], self.verb_video_preds, self.verb_video_labels, self.clip_count),
+                                     (preds[1], labels[1], self.noun_video_preds, self.noun_video_labels, self._noun_count)):
+            l = l.detach().to(self.device, torch.int64, non_blocking=True).contiguous()
+            ops.view_accumulate(p.detach(), ids, l, self.num_clips, table, tl, cnt, self.flag, "sum")
+        if host_ids is None:
+            host_ids = clip_ids.detach().cpu()                  # ids that only exist on the device: the one sync of this path
+        for ind, cid in enumerate(host_ids.tolist()):
+            if 0 <= cid < self.metadata.shape[0] * self.num_clips:
+                self.metadata[int(cid) // self.num_clips] = metadata["narration_id"][ind]
+
+    def finalize_metrics(self, ks=(1, 5)):
+        from focus_amd import ops
+        acc_i = torch.zeros(_NI, dtype=torch.int64, device=self.device)
+        acc_f = torch.zeros(_NF, dtype=torch.float64, device=self.device)
+        ops.topk_stats(acc_i, acc_f, (self.verb_video_preds, self.noun_video_preds),
+                       (self.verb_video_labels, self.noun_video_labels), ks)
+        t = torch.cat([acc_i, self.flag.to(torch.int64)]).cpu()
+        assert not int(t[_NI]) & 2, "a clip id lies outside [0, num_videos * num_clips)"
+        n = self.verb_video_preds.size(0)
+        stats = {"split": "test_final"}
+        for h, name in enumerate(("verb", "noun", "action")):
+            for j, k in enumerate(ks):
+                x = torch.tensor(float(t[_CORRECT + 4 * h + j]))
+                stats["{}_top{}_acc".format(name, k)] = "{:.{prec}f}".format(float((x / n) * 100.0), prec=2)
+        self.stats = stats
+        return (self.verb_video_preds.cpu().numpy().copy(), self.noun_video_preds.cpu().numpy().copy()), \
+               (self.verb_video_labels.cpu().numpy().copy(), self.noun_video_labels.cpu().numpy().copy()), \
+               self.metadata.copy()

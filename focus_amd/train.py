@@ -14,7 +14,10 @@ import torch
 from .slowfast.utils import misc
 
 
-def train_step(model, optimizer, loss_fun, inputs, labels, meta, cfg, check_nan=True):
+def train_step(model, optimizer, loss_fun, inputs, labels, meta, cfg, check_nan=True, stats=None):
+    """`stats`: a meters.StepStats.  The step's loss (for epickitchens also verb_loss and noun_loss), the top-k counts and the
+    NaN guard then go into its device tables by one launch right after the loss; the host NaN check is not made whatever
+    `check_nan` says, and a NaN surfaces at the next stats.read().  Labels may be the dense rows of mixup."""
     preds = model(inputs, meta)                                   # train_net.py:86
     extra_preds = None
     if isinstance(preds, tuple):                                  # :87-88 (EK: (verb, {'verb','noun'}))
@@ -24,7 +27,12 @@ def train_step(model, optimizer, loss_fun, inputs, labels, meta, cfg, check_nan=
         loss = loss_dict["verb_loss"] + loss_dict["noun_loss"]
     else:
         loss = loss_fun(preds, labels)                            # :99
-    if check_nan:
+    if stats is not None:
+        if cfg.TRAIN.DATASET == "epickitchens":
+            stats.update(extra_preds, labels, loss, (loss_dict["verb_loss"], loss_dict["noun_loss"]))
+        else:
+            stats.update(preds, labels, loss)
+    elif check_nan:
         misc.check_nan_losses(float(loss.detach()))                        # :102 (host sync, as in the reference)
     optimizer.zero_grad(set_to_none=True)                         # :105
     loss.backward()                                               # :106
@@ -73,13 +81,18 @@ def mixup_collapse(preds, labels):
     return preds, top2[:, 0]
 
 
-def train_iter(model, optimizer, loss_fun, inputs, labels, meta, cfg, mixup_fn=None, check_nan=True):
+def train_iter(model, optimizer, loss_fun, inputs, labels, meta, cfg, mixup_fn=None, check_nan=True, stats=None):
     """One iteration of train_net.py:78-149 around the unchanged train_step: the optional mixup of inputs[0] and the labels
     (:78-80), the step (:82-121), and with mixup the collapse of the dense labels for the metrics (:123-149).  Returns
     (preds, labels, loss) ready for metrics.topk_errors; for epickitchens `preds` is the {'verb','noun'} dict when mixing
-    was on (what the reference scores there), else what train_step returned."""
+    was on (what the reference scores there), else what train_step returned.
+    With `stats` (a meters.StepStats, see train_step) the dense labels go straight into its kernel, which collapses them
+    itself: there is no mixup_collapse, and the predictions and labels are returned as the step used them."""
     if mixup_fn is not None:
         inputs[0], labels = mixup_fn(inputs[0], labels)
+    if stats is not None:
+        preds, loss = train_step(model, optimizer, loss_fun, inputs, labels, meta, cfg, check_nan=check_nan, stats=stats)
+        return preds, labels, loss
     if mixup_fn is None or cfg.TRAIN.DATASET != "epickitchens":
         preds, loss = train_step(model, optimizer, loss_fun, inputs, labels, meta, cfg, check_nan=check_nan)
     else:
@@ -96,10 +109,12 @@ def train_iter(model, optimizer, loss_fun, inputs, labels, meta, cfg, mixup_fn=N
     return preds, labels, loss
 
 
-def slot_train_step(model, optimizer, video, global_step, cfg, noise=None):
+def slot_train_step(model, optimizer, video, global_step, cfg, noise=None, stats=None):
     """One iteration of slot_train_epoch (tools/steve_train_net.py:57-126): schedules -> forward -> mse + cross_entropy ->
     NaN check -> zero_grad -> backward -> clip-norm -> step.  Returns (loss, mse, cross_entropy, recon, attns, tau).
-    TRAIN.MIXED_PRECISION selects bf16 storage inside the model (no autocast / GradScaler: see the module docstring)."""
+    TRAIN.MIXED_PRECISION selects bf16 storage inside the model (no autocast / GradScaler: see the module docstring).
+    `stats`: a meters.StepStats(device, ks=(), aux_names=("mse", "cross_entropy")); loss, mse and cross_entropy then go into
+    its device tables and the host NaN check is left to the next stats.read()."""
     import math
     from .slowfast.models import optimizer as optim
     from .slowfast.utils import lr_policy as lrp
@@ -114,7 +129,10 @@ def slot_train_step(model, optimizer, video, global_step, cfg, noise=None):
     mse = mse.mean()                                                                                  # :101-102
     cross_entropy = cross_entropy.mean()
     loss = mse + cross_entropy                                                                        # :104
-    misc.check_nan_losses(float(loss.detach()))                                                       # :108
+    if stats is not None:
+        stats.update(None, None, loss, (mse, cross_entropy), batch=video.shape[0])
+    else:
+        misc.check_nan_losses(float(loss.detach()))                                                   # :108
     optimizer.zero_grad()                                                                             # :111
     loss.backward()
     if (cfg.SOLVER.CLIP_GRAD_VAL or cfg.SOLVER.CLIP_GRAD_L2NORM) and optim.fused_route(model, optimizer):
@@ -190,22 +208,83 @@ def slot_eval_epoch(eval_loader, model, cfg=None):
 
 
 @torch.no_grad()
-def perform_test(test_loader, model, test_meter, cfg):
-    """Multi-view testing (tools/test_net.py:24-157, single-label branch): every clip of every video goes through the
-    model in eval mode (softmax scores), the meter sums the views per video.  `test_loader` yields
-    (inputs, labels, video_idx, meta) like the reference's loaders."""
+def eval_epoch(val_loader, model, cfg, stats=None):
+    """The validation loop (tools/train_net.py:311-470, the single-label and the epickitchens branch): eval mode, no
+    gradients, `val_loader` yields (inputs, labels, _, meta).  Every batch is one meters.StepStats.update (made here when
+    none is given) and nothing is read until the end: one read, then the epoch's figures -- top-k errors, or verb / noun /
+    action accuracies -- over all samples (and ranks) are returned."""
+    from .slowfast.utils import meters
     model.eval()
     dev = next(model.parameters()).device
+    ek = zero = None
+    for inputs, labels, _, meta in val_loader:
+        inputs = [x.to(dev) for x in inputs] if isinstance(inputs, (list, tuple)) else inputs.to(dev)
+        meta = {k: (v.to(dev) if isinstance(v, torch.Tensor) else v) for k, v in meta.items()}
+        ek = isinstance(labels, dict) and cfg.TRAIN.DATASET == "epickitchens"                    # :372
+        labels = {k: v.to(dev) for k, v in labels.items()} if isinstance(labels, dict) else labels.to(dev)
+        if stats is None:
+            stats = meters.StepStats(dev, multitask=ek)
+        if zero is None:
+            zero = torch.zeros((), device=dev)                                                  # the loop computes no loss
+        preds = model(inputs, meta)
+        extra_preds = None
+        if isinstance(preds, tuple):
+            preds, extra_preds = preds
+        if ek:
+            stats.update(extra_preds, labels, zero, (zero, zero))
+        else:
+            stats.update(preds, labels, zero)
+    if stats is None:
+        return {}
+    stats.read()
+    return stats.epoch_stats()
+
+
+def _takes_metadata(meter):
+    import inspect
+    try:
+        return "metadata" in inspect.signature(meter.update_stats).parameters
+    except (TypeError, ValueError, AttributeError):
+        return False
+
+
+@torch.no_grad()
+def perform_test(test_loader, model, test_meter, cfg):
+    """Multi-view testing (tools/test_net.py:24-157): every clip of every video goes through the
+    model in eval mode (softmax scores), the meter sums the views per video.  `test_loader` yields
+    (inputs, labels, video_idx, meta) like the reference's loaders.  Dict labels, or a meter whose update_stats takes
+    `metadata` (meters.EPICTestMeter), take the epickitchens branch (:85-111): both heads and the narration ids go to the
+    meter.  A meters.DeviceTestMeter receives device tensors as they are, without a copy to the host."""
+    from .slowfast.utils import meters
+    model.eval()
+    dev = next(model.parameters()).device
+    ek_meter = _takes_metadata(test_meter)
+    on_device = isinstance(test_meter, (meters.DeviceTestMeter, meters.EPICTestMeter))
     for inputs, labels, video_idx, meta in test_loader:
         inputs = [x.to(dev) for x in inputs] if isinstance(inputs, (list, tuple)) else inputs.to(dev)
         meta = {k: (v.to(dev) if isinstance(v, torch.Tensor) else v) for k, v in meta.items()}
         preds = model(inputs, meta)
+        if isinstance(labels, dict) or ek_meter:
+            extra_preds = preds[1]
+            distributed = torch.distributed.is_available() and torch.distributed.is_initialized() and \
+                torch.distributed.get_world_size() > 1
+            if distributed:
+                raise NotImplementedError("the multi-rank gather of narration ids (test_net.py:87-98) is not part of this path")
+            args = ((extra_preds["verb"], extra_preds["noun"]), (labels["verb"], labels["noun"]), meta, video_idx)
+            if not on_device:
+                args = (tuple(p.detach().cpu() for p in args[0]), tuple(l.detach().cpu() for l in args[1]), meta,
+                        video_idx.detach().cpu())
+            test_meter.update_stats(*args)
+            continue
         if isinstance(preds, tuple):
             preds = preds[0]
         if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
             from .slowfast.utils import distributed as du
             preds, labels, video_idx = du.all_gather([preds, labels.to(dev), video_idx.to(dev)])
         test_meter.update_stats(preds, labels, video_idx)
+    if ek_meter:
+        test_meter.finalize_metrics()
+        return test_meter.stats
     return test_meter.finalize_metrics()
 
 

@@ -866,6 +866,55 @@ int focus_slot_boxes(const int32_t* stats, int B, int T, int K, int He, int We, 
 int focus_seg_contingency(const uint8_t* seg, const void* truth, int truth_is_f32, int B, int T, int S, int H, int W, int He,
                           int We, int K, int first_segment, int32_t* table, void* stream);
 
+/* -------------------------------------------------------------------------------------------------
+ * Step and test statistics on the device (step_stats.hip): what the loops of tools/train_net.py:123-269, :311-470 and
+ * tools/test_net.py:85-128 do with the predictions, without a host round trip.  Counts are integers (integer atomics:
+ * the same in any arrival order); the double sums are touched by exactly one thread per launch; no float atomics.
+ *
+ * focus_topk_stats: adds one batch into an accumulator that stays on the device.  No argument varies from step to step
+ *   (the step counter lives in the accumulator), so the launch can sit inside a captured step.
+ *     heads in {0, 1, 2}; per head h: logits [B, V_h], row stride ld_h in elements, dtype_h FOCUS_F32 or FOCUS_BF16, and
+ *     labels: int64 [B] (dense_labels == 0) or dense fp32 [B, V_h] with row stride ldl_h (dense_labels != 0, the mixup
+ *     targets).  nk values k0 < k1 < ... (nk <= 4; the others are not looked at).  loss0..2: device fp32 scalars, any may
+ *     be NULL.  acc_i: int64 [16] = steps, samples, nan (0 / 1), nan_step, correct[3][4] (row h, column = index into ks;
+ *     row 2 = every head); acc_f: float64 [8] = loss_sum[3], loss_weighted[3], 2 unused.  Both start as zeros.
+ *   Order: entry (x, i) beats (y, j) if exactly one of x, y is NaN and it is x; otherwise if x > y, or x == y and i < j
+ *     (NaN greatest as in torch.topk, ties to the lowest index as in focus_greedy_next).  A row is correct at k when
+ *     fewer than k entries of its row beat the label's entry; a label outside [0, V) is never correct.
+ *   Dense labels (train_net.py:123-149): first = the greatest entry of the label row by that order, second = the greatest
+ *     of the rest (several NaNs in a label row: the lowest index first).  The row is scored as if pred[first] = pred[first] +
+ *     pred[second], the sum formed in fp32 and rounded once to the logits' dtype, and pred[second] = 0; the label is first.
+ *     The logits are not written.
+ *   correct[0], correct[1] count per head; correct[2] counts rows correct in every head at that k (with one head it equals
+ *     correct[0]).  steps += 1, samples += B; for each non-NULL loss_i: loss_sum[i] += (double)loss_i, loss_weighted[i] +=
+ *     (double)loss_i * B, by one thread, so the sums are the bits of the same double sums formed on the host in step order.
+ *     If loss0 is NaN (inf passes) and nan == 0: nan = 1, nan_step = the value steps had before this launch.
+ *     heads == 0 updates only these scalars.
+ *   Status, before any launch (a refused call writes nothing): FOCUS_ERR_NULL (acc_i or acc_f); FOCUS_ERR_SHAPE (heads
+ *     outside 0..2); FOCUS_ERR_NULL (logits or labels of a head in use); with heads > 0 FOCUS_ERR_SHAPE (nk outside 1..4, a
+ *     k < 1 or not above the one before, the largest k above some V_h, V_h < 1, V_h < 2 with dense labels, ld_h < V_h, ldl_h <
+ *     V_h with dense labels) and FOCUS_ERR_DTYPE (logits neither fp32 nor bf16); FOCUS_OK without a launch for B <= 0.
+ *
+ * focus_view_accumulate: the multi-view ensembling of meters.py:300-332 / :1181-1201 for one head.  preds [n, C] fp32 or
+ *   bf16 with row stride ld, clip_ids and labels int64 [n] on the device; row i belongs to video clip_ids[i] / num_clips.
+ *   video_preds fp32 [num_videos, C], video_labels and clip_count int64 [num_videos], flag int32 [1] (sticky: bits are only
+ *   ever set).  Rows of the batch that share a video are folded in ascending row order by one owner (the first such row),
+ *   starting from the table's row: FOCUS_VIEW_SUM gives the bits of the reference's per-clip fp32 loop whatever the batch
+ *   split, FOCUS_VIEW_MAX is torch.max (a NaN stays).  Walking its rows in the same order the owner sets bit 0 of flag when
+ *   a clip's label differs from a non-zero label stored for the video (the label is written either way) and adds the rows
+ *   to clip_count.  A clip id outside [0, num_videos * num_clips) is skipped and sets bit 1.
+ *   Status, before any launch: FOCUS_ERR_NULL (any pointer); FOCUS_ERR_SHAPE (num_clips < 1, num_videos < 0, C < 1,
+ *     C > 65535 * 256, ld < C, an unknown mode); FOCUS_ERR_DTYPE; FOCUS_OK without a launch for n <= 0.
+ * ----------------------------------------------------------------------------------------------*/
+enum focus_view_mode { FOCUS_VIEW_SUM = 0, FOCUS_VIEW_MAX = 1 };
+int focus_topk_stats(int heads, int B, const void* logits0, int dtype0, int V0, int64_t ld0, const void* labels0, int64_t ldl0,
+                     const void* logits1, int dtype1, int V1, int64_t ld1, const void* labels1, int64_t ldl1, int dense_labels,
+                     int nk, int k0, int k1, int k2, int k3, const float* loss0, const float* loss1, const float* loss2,
+                     int64_t* acc_i, double* acc_f, void* stream);
+int focus_view_accumulate(const void* preds, int dtype, int n, int C, int64_t ld, const int64_t* clip_ids, const int64_t* labels,
+                          int num_clips, int num_videos, int mode, float* video_preds, int64_t* video_labels,
+                          int64_t* clip_count, int32_t* flag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
