@@ -3062,6 +3062,82 @@ def soft_target_ce(logits, target, reduction="mean"):
 
 
 # --------------------------------------------------------------------------------------------------
+# Random erasing of normalised clips in place (random_erase.hip; the plans come from slowfast/datasets/random_erasing.py)
+# --------------------------------------------------------------------------------------------------
+ERASE_MODES = ("const", "rand", "pixel")                                   # enum focus_erase_mode
+ERASE_ITEM_FIELDS = ("clip", "t0", "t1", "top", "left", "h", "w")         # focus_erase_item, in front of `ord`
+ERASE_MAX_PER_CLIP = 64                                                    # FOCUS_ERASE_MAX_PER_CLIP
+
+
+def erase_table(items, B, T, H, W):
+    """The host image of the focus_erase_item table: int32 [n, 8], and the largest number of items one clip has.  items:
+    mappings with clip, t0, t1, top, left, h, w; the items of one clip are applied in the order they are listed (a later one
+    wins where they overlap) and are made contiguous here.  A rectangle or frame range that is empty or leaves the
+    [B, T, H, W] tensor, or more than ERASE_MAX_PER_CLIP items for one clip, is a ValueError: the kernel cannot report it."""
+    import numpy as np
+    per_clip = {}
+    for n, it in enumerate(items):
+        try:
+            v = [it[k] for k in ERASE_ITEM_FIELDS]
+        except (KeyError, TypeError, IndexError):
+            raise ValueError("focus_amd: erase item %d is not a mapping with %s" % (n, ", ".join(ERASE_ITEM_FIELDS)))
+        if any(isinstance(a, bool) or not isinstance(a, (int, np.integer)) for a in v):
+            raise ValueError("focus_amd: erase item %d: %r are not all integers" % (n, v))
+        clip, t0, t1, top, left, h, w = (int(a) for a in v)
+        if not 0 <= clip < B:
+            raise ValueError("focus_amd: erase item %d: clip %d outside the batch of %d" % (n, clip, B))
+        if not 0 <= t0 < t1 <= T:
+            raise ValueError("focus_amd: erase item %d: frames [%d, %d) are empty or outside the %d frames" % (n, t0, t1, T))
+        if not (h >= 1 and w >= 1 and 0 <= top and top + h <= H and 0 <= left and left + w <= W):
+            raise ValueError("focus_amd: erase item %d: rectangle (top %d, left %d, h %d, w %d) is empty or outside the "
+                             "%dx%d frame" % (n, top, left, h, w, H, W))
+        rows = per_clip.setdefault(clip, [])
+        rows.append((clip, t0, t1, top, left, h, w, len(rows)))
+    most = max((len(r) for r in per_clip.values()), default=0)
+    if most > ERASE_MAX_PER_CLIP:
+        raise ValueError("focus_amd: %d erase items for one clip (at most %d)" % (most, ERASE_MAX_PER_CLIP))
+    rec = np.array([r for clip in sorted(per_clip) for r in per_clip[clip]], dtype=np.int32).reshape(-1, 8)
+    if rec.shape[0] > 65535:
+        raise ValueError("focus_amd: random_erase_ takes at most 65535 items per call (got %d)" % rec.shape[0])
+    return rec, most
+
+
+def random_erase_(x, items, mode, layout, seed=None):
+    """RandomErasing of a batch of clips IN PLACE, one launch: x [B,C,T,H,W] (layout "BCTHW") or [B,T,C,H,W] ("BTCHW"), fp32 or
+    bf16, contiguous -- what clip_sample returns.  items: see erase_table (datasets/random_erasing.RandomErasing.plan makes
+    them).  mode "const" writes +0.0, "rand" one N(0,1) value per (item, frame, channel), "pixel" one per element, from the
+    build-owned generator of include/focus_amd.h; `seed`: int32 [2] on x's device (default: drawn from torch's generator).
+    One H2D copy of the table, one launch; an empty item list launches nothing.  Returns x itself.  No CPU fallback."""
+    if layout not in ("BCTHW", "BTCHW"):
+        raise ValueError("focus_amd: random_erase_ layout is BCTHW or BTCHW (got %r)" % (layout,))
+    if mode not in ERASE_MODES:
+        raise ValueError("focus_amd: random_erase_ mode is one of %s (got %r)" % (", ".join(ERASE_MODES), mode))
+    if x.dim() != 5 or x.numel() == 0:
+        raise ValueError("focus_amd: random_erase_ needs a non-empty 5-d tensor (got shape %s)" % (tuple(x.shape),))
+    B, H, W = int(x.shape[0]), int(x.shape[3]), int(x.shape[4])
+    C, T = (int(x.shape[1]), int(x.shape[2])) if layout == "BCTHW" else (int(x.shape[2]), int(x.shape[1]))
+    if H > 32768 or W > 32768 or T > 65535 or C > 65535:
+        raise ValueError("focus_amd: random_erase_ takes frames up to 32768 a side and up to 65535 frames and channels")
+    rec, most = erase_table(items, B, T, H, W)
+    _need_dense(x, "random_erase_")
+    dt = _dt(x)
+    if seed is not None and (not seed.is_cuda or seed.device != x.device or seed.dtype != torch.int32 or seed.numel() < 2
+                             or not seed.is_contiguous()):
+        raise ValueError("focus_amd: random_erase_ seed is a contiguous int32 [2] tensor on the clips' device")
+    if rec.shape[0] == 0:
+        return x
+    plane = H * W
+    sc, st = (T * plane, plane) if layout == "BCTHW" else (plane, C * plane)
+    with torch.cuda.device(x.device):
+        if seed is None and mode != "const":
+            seed = torch.randint(-2 ** 31, 2 ** 31 - 1, (2,), device=x.device, dtype=torch.int32)
+        table = torch.from_numpy(rec).pin_memory().to(x.device, non_blocking=True)
+        _lib.check(_lib.lib().focus_random_erase(_p(x), dt, B, T, C, H, W, C * T * plane, sc, st, _p(table), rec.shape[0], most,
+                                                 ERASE_MODES.index(mode), _p(seed), _stream()), "random_erase")
+    return x
+
+
+# --------------------------------------------------------------------------------------------------
 # RandAugment on device uint8 clips (randaug.hip; the plans come from slowfast/datasets/rand_augment.py)
 # --------------------------------------------------------------------------------------------------
 RANDAUG_OPS = ("copy", "autocontrast", "equalize", "invert", "posterize", "solarize", "solarize_add", "brightness", "color",

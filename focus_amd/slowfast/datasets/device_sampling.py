@@ -6,8 +6,10 @@ random resized crop (the branch every shipped ORViT config takes: AUG.ENABLE wit
 views 0/1/2 -- resize a source rectangle to (rh, rw) and take a window of the result, so here the HOST only draws the
 reference's random numbers and moves the boxes (`sampling_params`, bit-identical to the reference) and ONE HIP launch
 produces the pixels of the whole batch (`ops.clip_sample`).  RandAugment runs in front of it, on the uint8 clips and on the
-device too (`augment_clips`: the host draws the reference's numbers and moves the boxes, `ops.randaug_apply` runs the ops);
-colour jitter and random erasing are not part of this path."""
+device too (`augment_clips`: the host draws the reference's numbers and moves the boxes, `ops.randaug_apply` runs the ops),
+and random erasing behind it, in place on the sampled batch (`erase_clips`: the host draws the reference's rectangles, ONE
+`ops.random_erase_` writes them).  `make_batch` chains the three.  That is every augmentation the reference's video datasets
+apply: AUG.COLOR_JITTER is read by its ImageNet dataset alone (imagenet.py:136)."""
 import math
 
 import numpy as np
@@ -15,6 +17,7 @@ import torch
 
 from ... import ops
 from . import transform
+from .random_erasing import RandomErasing
 from .utils import boxes_to_orvit_format
 
 
@@ -131,7 +134,8 @@ def augment_clips(cfg, clips_u8, boxes=None):
     them; otherwise one transform plans the whole clip (with `interpolation: random` its frames still draw their resample one
     by one).  The draws are the reference's, clip by clip and frame by frame in order; ONE ops.randaug_apply runs the batch.
     Returns (clips_u8, boxes) for sample_clips: new tensors and new box arrays, or the inputs themselves when AUG.ENABLE is
-    false or AUG.AA_TYPE is empty.  AUG.RE_PROB and AUG.COLOR_JITTER are not read: they stay the reference's."""
+    false or AUG.AA_TYPE is empty.  AUG.RE_PROB belongs to erase_clips; AUG.COLOR_JITTER is not read, as in the reference's video
+    datasets (only imagenet.py:136 reads it)."""
     aug = getattr(cfg, "AUG", None)
     aa_type = getattr(aug, "AA_TYPE", "") if aug is not None else ""
     if aug is None or not getattr(aug, "ENABLE", False) or not aa_type:
@@ -160,3 +164,40 @@ def augment_clips(cfg, clips_u8, boxes=None):
         plans.append(frames)
         out_boxes.append(b)
     return ops.randaug_apply(clips_u8, plans), (None if boxes is None else out_boxes)
+
+
+def erase_clips(cfg, inputs):
+    """The device form of ssv2.py:436-446 (the end of `_aug_frame`; kinetics.py:398-410 and epickitchens.py:347-359 alike):
+    RandomErasing of a sampled batch under cfg.AUG, in place.  inputs: what sample_clips returned, [B,3,T,S,S] or for
+    MODEL.MODEL_NAME "STEVE" [B,T,3,S,S].  Every clip gets the reference's transform -- RandomErasing(AUG.RE_PROB,
+    mode=AUG.RE_MODE, max_count=AUG.RE_COUNT, num_splits=AUG.RE_COUNT) -- and its draws from Python's `random`, clip by clip
+    in order; ONE ops.random_erase_ writes the rectangles of the batch.  The fill values come from the build-owned generator,
+    seeded from torch's (ops.random_erase_).  Returns `inputs` itself; untouched when AUG.ENABLE is false or AUG.RE_PROB is
+    not above 0."""
+    aug = getattr(cfg, "AUG", None)
+    prob = getattr(aug, "RE_PROB", 0.25) if aug is not None else 0.0
+    if aug is None or not getattr(aug, "ENABLE", False) or not prob > 0:
+        return inputs
+    if inputs.dim() != 5:
+        raise ValueError("erase_clips takes the 5-d batch sample_clips returns (got shape %s)" % (tuple(inputs.shape),))
+    mode, count = getattr(aug, "RE_MODE", "pixel"), getattr(aug, "RE_COUNT", 1)
+    layout = "BTCHW" if cfg.MODEL.MODEL_NAME == "STEVE" else "BCTHW"
+    T = int(inputs.shape[1] if layout == "BTCHW" else inputs.shape[2])
+    H, W = int(inputs.shape[3]), int(inputs.shape[4])
+    items = []
+    for b in range(inputs.shape[0]):
+        erase = RandomErasing(prob, mode=mode, max_count=count, num_splits=count, device="cpu")
+        items += [dict(it, clip=b) for it in erase.plan(T, H, W) if it["h"] > 0 and it["w"] > 0 and it["t0"] < it["t1"]]
+    return ops.random_erase_(inputs, items, erase.mode, layout)
+
+
+def make_batch(cfg, clips_u8, boxes, spatial_idx=-1, **sampling):
+    """Decoded uint8 clips and their boxes -> (inputs, orvit_bboxes), every stage on the device.  Training (spatial_idx -1):
+    augment_clips -> sample_clips -> erase_clips, what Ssv2._aug_frame does to a clip under AUG.ENABLE (without AUG the first
+    and the last return their inputs); the test views 0/1/2: sample_clips alone.  `sampling` goes to sample_clips.  The
+    draws are consumed stage by stage, each stage clip by clip."""
+    if spatial_idx != -1:
+        return sample_clips(cfg, clips_u8, boxes, spatial_idx, **sampling)
+    clips_u8, boxes = augment_clips(cfg, clips_u8, boxes)
+    inputs, orvit_bboxes = sample_clips(cfg, clips_u8, boxes, spatial_idx, **sampling)
+    return erase_clips(cfg, inputs), orvit_bboxes

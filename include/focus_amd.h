@@ -915,6 +915,58 @@ int focus_view_accumulate(const void* preds, int dtype, int n, int C, int64_t ld
                           int num_clips, int num_videos, int mode, float* video_preds, int64_t* video_labels,
                           int64_t* clip_count, int32_t* flag, void* stream);
 
+/* -------------------------------------------------------------------------------------------------
+ * Random erasing (random_erase.hip; datasets/random_erasing.py of the reference, the last step of Ssv2._aug_frame): rectangles
+ * of a batch of normalised clips are overwritten IN PLACE, in one launch.  x is the tensor focus_clip_sample wrote and is
+ * addressed the same way: element (b, c, t, y, x) lives at  b*sb + c*sc + t*st + y*W + x  (strides in elements, rows and
+ * planes of H x W dense), so one entry point serves [B,C,T,H,W] and [B,T,C,H,W], fp32 and bf16.
+ *
+ * `items`: DEVICE array of n_items descriptors owned by the caller.  An item erases the rectangle [top, top+h) x
+ * [left, left+w) of every channel of the frames [t0, t1) of clip `clip`.  The items of one clip are CONTIGUOUS in the table
+ * and stand in the order the reference writes them: where rectangles of one clip overlap, every pixel gets the value of the
+ * LAST item of its clip that covers it -- the thread that owns a pixel of item i looks at the up to max_per_clip - 1 items
+ * behind i, and leaves the pixel alone when one of them has the same clip and covers it too.  So the result does not depend on
+ * scheduling; max_per_clip is the largest number of items any clip has in the table (1: nothing is scanned).  `ord` is the
+ * item's ordinal within its clip; it feeds the generator and nothing else.
+ *
+ * What is written, by mode:
+ *   FOCUS_ERASE_CONST  +0.0
+ *   FOCUS_ERASE_RAND   one N(0,1) value per (item, frame, channel):  zc(ord, clip, t, c, 0xffffffff)
+ *   FOCUS_ERASE_PIXEL  one N(0,1) value per (item, frame, channel, y, x):  with p = (y << 16) | (x >> 1),
+ *                      zc(ord, clip, t, c, p) in an even column x and zs(ord, clip, t, c, p) in an odd one
+ * with the build-owned counter-based generator (mix32 = lowbias32, as in gumbel.hip; all integer arithmetic mod 2^32):
+ *     k  = mix32(mix32(mix32(seed[0] ^ clip) + ord * 0x9E3779B9) ^ t) + c * 0x9E3779B9
+ *     ha = mix32(mix32(k) ^ p),   hb = mix32(ha ^ seed[1])
+ *     u1 = ((ha >> 9) + 0.5) / 2^23  in (0, 1),   u2 = (hb >> 8) / 2^24  in [0, 1)          (both exact in fp32)
+ *     r  = sqrtf(-2 logf(u1)),   zc = r * cospif(2 u2),   zs = r * sinpif(2 u2)              (Box-Muller, fp32: the two
+ *                                                                   values of one draw are independent N(0,1) values)
+ * t, c, y, x are LOGICAL coordinates of the tensor, so both layouts, both dtypes and any launch geometry give the same
+ * number; bf16 is one round-to-nearest-even of the fp32 value.  |z| <= sqrt(2 ln 2^24) = 5.77.  `seed`: two 32-bit words on
+ * the DEVICE (not read for FOCUS_ERASE_CONST, where it may be NULL).  The reference draws the fill from torch's CPU generator:
+ * the distribution here is the reference's, the draws are not (as for the decoder's dropout, focus_dropout_add).
+ *
+ * The kernel only writes: it reads the table and the seed, and neither reads nor writes a byte of x outside the rectangles.
+ * Rows start at an arbitrary `left`: the 16-byte-aligned body of a row is written with 16-byte stores, its ends element by
+ * element.  No workspace, no atomics: the same arguments give the same bits.
+ *
+ * The table lives on the device, so this entry point cannot judge it.  The kernel clamps every rectangle to [0,H) x [0,W)
+ * and every frame range to [0,T), and skips an item that is empty afterwards or whose clip is outside [0,B), so a bad
+ * descriptor cannot write outside the tensor (focus_amd.ops.random_erase_ raises ValueError for every such item instead).
+ *
+ * Status, judged in this order before any launch (a refused call writes nothing): FOCUS_ERR_NULL (x or items is NULL; seed is
+ * NULL in a mode that draws); FOCUS_OK without a launch for n_items <= 0; FOCUS_ERR_SHAPE (an unknown mode; B, T, C, H or W
+ * < 1; H or W > 32768; T, C or n_items > 65535; max_per_clip outside [1, FOCUS_ERASE_MAX_PER_CLIP]; sb < 1, sc < H*W or
+ * st < H*W); FOCUS_ERR_DTYPE (neither FOCUS_F32 nor FOCUS_BF16); FOCUS_ERR_ALIGN (x not aligned to its element size).
+ * ----------------------------------------------------------------------------------------------*/
+#define FOCUS_ERASE_MAX_PER_CLIP 64
+enum focus_erase_mode { FOCUS_ERASE_CONST = 0, FOCUS_ERASE_RAND = 1, FOCUS_ERASE_PIXEL = 2 };
+typedef struct focus_erase_item {
+    int32_t clip, t0, t1, top, left, h, w, ord;
+} focus_erase_item;
+int focus_random_erase(void* x, int dtype, int B, int T, int C, int H, int W, int64_t sb, int64_t sc, int64_t st,
+                       const focus_erase_item* items, int n_items, int max_per_clip, int mode, const void* seed,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif
