@@ -3336,6 +3336,82 @@ def seg_contingency(seg, truth, He, We, K, first_segment=1):
 
 
 # --------------------------------------------------------------------------------------------------
+# STEVE epoch visualisation (csrc/slot_vis.hip)
+# --------------------------------------------------------------------------------------------------
+SLOT_FORM_VIS, SLOT_FORM_RAW = 0, 1           # enum focus_slot_form
+VIS_OUT_F32, VIS_OUT_U8 = 0, 1                # enum focus_vis_out
+
+
+def slot_vis_grid_shape(T, H, W, K, rows):
+    """[1,T,3,Hg,Wg] of make_grid(nrow=K+3, padding=2) over `rows` clips."""
+    return (1, int(T), 3, int(rows) * (int(H) + 2) + 2, (int(K) + 3) * (int(W) + 2) + 2)
+
+
+def slot_vis_grid(video, recon, gen, *, attns_vis=None, attn=None, grid=None, rows=8, out_dtype=torch.float32):
+    """slot_misc.visualize's video in one launch: per frame the grid of `rows` clips x (video, recon, gen, K slot overlays)
+    tiles, 2 pixels of 0.8 between and around them -> [1,T,3,Hg,Wg].  video, recon [B,T,3,H,W] and gen [Bg,T,3,H,W] are fp32
+    or bf16, each on its own.  The overlays come from exactly one of
+      attns_vis [B,T,K,3,H,W] fp32 (what STEVE.forward / encode return): copied;
+      attn [B,T,He*We,K] fp32 or bf16 (the slot update's attention) with grid=(He, We), He | H and We | W: the overlay
+        video * a + (1 - a) of the nearest-upsampled mask, in the reference's three fp32 roundings, made on the fly.
+    rows is clamped to B, as slicing [:N] does; gen must hold that many clips.  out_dtype float32 gives the reference's
+    bits, uint8 what TensorBoard's add_video makes of them ((x * 255).clip(0, 255), truncated; NaN -> 0).  No CPU fallback."""
+    if (attns_vis is None) == (attn is None):
+        raise ValueError("focus_amd: slot_vis_grid takes exactly one of attns_vis and attn")
+    if (attn is None) != (grid is None):
+        raise ValueError("focus_amd: slot_vis_grid takes grid=(He, We) with attn, and only with it")
+    if out_dtype not in (torch.float32, torch.uint8):
+        raise ValueError("focus_amd: slot_vis_grid writes float32 or uint8 (got %s)" % (out_dtype,))
+    if video.dim() != 5 or video.shape[2] != 3 or min(video.shape) < 1:
+        raise ValueError("focus_amd: slot_vis_grid takes a non-empty video [B,T,3,H,W]; got %s" % (tuple(video.shape),))
+    B, T, _, H, W = (int(s) for s in video.shape)
+    if tuple(recon.shape) != tuple(video.shape) or gen.dim() != 5 or tuple(gen.shape[1:]) != tuple(video.shape[1:]) \
+            or gen.shape[0] < 1:
+        raise ValueError("focus_amd: slot_vis_grid: recon %s and gen %s do not match video %s" % (
+            tuple(recon.shape), tuple(gen.shape), tuple(video.shape)))
+    rows = min(int(rows), B)
+    if rows < 1 or rows > gen.shape[0]:
+        raise ValueError("focus_amd: slot_vis_grid: %d rows asked of a gen of %d clips (at least 1)" % (rows, gen.shape[0]))
+    slots = attn if attns_vis is None else attns_vis
+    if attns_vis is not None:
+        if slots.dim() != 6 or tuple(slots.shape[:2]) != (B, T) or tuple(slots.shape[3:]) != (3, H, W) \
+                or not 1 <= slots.shape[2] <= 32:
+            raise ValueError("focus_amd: slot_vis_grid takes attns_vis [B,T,K,3,H,W] with 1 <= K <= 32; got %s for video %s" % (
+                tuple(slots.shape), tuple(video.shape)))
+        if slots.dtype != torch.float32:
+            raise ValueError("focus_amd: slot_vis_grid: attns_vis is float32 (got %s)" % slots.dtype)
+        K, He, We, form = int(slots.shape[2]), 1, 1, SLOT_FORM_VIS
+    else:
+        try:
+            He, We = (int(g) for g in grid)
+        except (TypeError, ValueError):
+            raise ValueError("focus_amd: slot_vis_grid: grid is (He, We); got %r" % (grid,))
+        if He < 1 or We < 1 or H % He or W % We:
+            raise ValueError("focus_amd: slot_vis_grid: the %dx%d slot grid does not divide the %dx%d frame" % (He, We, H, W))
+        if slots.dim() != 4 or tuple(slots.shape[:3]) != (B, T, He * We) or not 1 <= slots.shape[3] <= 32:
+            raise ValueError("focus_amd: slot_vis_grid takes attn [B,T,He*We,K] with 1 <= K <= 32; got %s for video %s and a "
+                             "%dx%d grid" % (tuple(slots.shape), tuple(video.shape), He, We))
+        K, form = int(slots.shape[3]), SLOT_FORM_RAW
+    shape = slot_vis_grid_shape(T, H, W, K, rows)
+    if T * 3 * shape[3] * shape[4] >= 2 ** 31:
+        raise ValueError("focus_amd: slot_vis_grid: a video of %s has 2^31 elements or more" % (shape,))
+    for name, t in (("video", video), ("recon", recon), ("gen", gen), ("attn", slots)):
+        if t.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("focus_amd: slot_vis_grid: %s is float32 or bfloat16 (got %s)" % (name, t.dtype))
+        _need_contiguous(t, "slot_vis_grid's %s" % name)
+        if t.device != video.device:
+            raise ValueError("focus_amd: slot_vis_grid: %s is on %s, video on %s" % (name, t.device, video.device))
+    _need_gpu(video)
+    out = torch.empty(shape, device=video.device, dtype=out_dtype)
+    with torch.cuda.device(video.device):
+        _lib.check(_lib.lib().focus_slot_vis_grid(
+            _p(video), _dt(video), _p(recon), _dt(recon), _p(gen), _dt(gen), _p(slots), _dt(slots), form, B, int(gen.shape[0]),
+            T, 3, H, W, K, He, We, rows, _p(out), VIS_OUT_U8 if out_dtype == torch.uint8 else VIS_OUT_F32, _stream()),
+            "slot_vis_grid")
+    return out
+
+
+# --------------------------------------------------------------------------------------------------
 # Step and test statistics (csrc/step_stats.hip)
 # --------------------------------------------------------------------------------------------------
 STATS_INTS, STATS_FLOATS = 16, 8      # the two accumulator tables of focus_topk_stats (include/focus_amd.h)

@@ -427,6 +427,7 @@ class STEVE(nn.Module):
         # into a pair of HIP graphs (torch.cuda.make_graphed_callables) and replayed inside the eager training step
         self.graph_slot_update = bool(args.SLOTS.get("GRAPH_SLOT_UPDATE", False))
         self._savi_graphs = {}
+        self.slot_grid = None                         # (H_enc, W_enc) of the last encoder pass
         self.dvae = dVAE(args.SLOTS.VOCAB_SIZE, args.SLOTS.IMG_CHANNELS)
         self.steve_encoder = STEVEEncoder(args)
         self.steve_decoder = STEVEDecoder(args)
@@ -486,6 +487,7 @@ class STEVE(nn.Module):
         enc = self.steve_encoder
         emb = enc.pos(self._conv(enc.cnn, self._frames(video)))                                       # B*T, d_model, H_enc, W_enc
         H_enc, W_enc = emb.shape[-2:]
+        self.slot_grid = (int(H_enc), int(W_enc))     # the grid of the last call: what forward(..., attns="raw")'s N means
         emb_set = emb.permute(0, 2, 3, 1).flatten(start_dim=1, end_dim=2).to(self.compute_dtype)    # B*T, H_enc*W_enc, d_model
         ln = enc.layer_norm
         emb_set = ops.mlp(ops.layer_norm(emb_set, ln.weight, ln.bias, ln.eps), enc.mlp[0].weight, enc.mlp[0].bias,
@@ -522,7 +524,12 @@ class STEVE(nn.Module):
             torch.cuda.set_rng_state(state, emb_set.device)
         return g(emb_set, noise)
 
-    def forward(self, video, tau, hard, noise=None):
+    def forward(self, video, tau, hard, noise=None, attns="vis"):
+        """attns="vis" (the reference's return): the overlays [B,T,K,C,H,W] in fp32.  attns="raw": the slot update's attention
+        [B,T,N,K] itself, detached, in its own dtype -- no upsampled masks and no overlays are made (utils/slot_misc.
+        visualize_slots draws the same pictures from it); recon, cross_entropy and mse are the same bits either way."""
+        if attns not in ("vis", "raw"):
+            raise ValueError("STEVE.forward: attns is 'vis' or 'raw' (got %r)" % (attns,))
         B, T, C, H, W = video.size()
         noise = noise or {}
         dec = self.steve_decoder
@@ -568,8 +575,12 @@ class STEVE(nn.Module):
         dvae_recon = recon_flat.reshape(B, T, C, H, W)
 
         # slots (:277-300)
-        slots, attns = self._slots(video, noise.get("slots"))
-        attns = video.unsqueeze(2) * attns + (1.0 - attns)                                # B, T, K, C, H, W
+        if attns == "raw":
+            slots, attns, _, _ = self._slot_attns(video, noise.get("slots"))
+            attns = attns.detach()                                                        # B, T, N, K
+        else:
+            slots, attns = self._slots(video, noise.get("slots"))
+            attns = video.unsqueeze(2) * attns + (1.0 - attns)                            # B, T, K, C, H, W
 
         # decode (:303-306): cross entropy of the hard tokens under the decoder's prediction, summed over the tokens
         slots = ops.linear(slots, self.steve_encoder.slot_proj.weight)                    # B, T, K, d_model
@@ -652,5 +663,5 @@ class STEVE(nn.Module):
     def reconstruct_autoregressive(self, video):
         """steve.py:383-392."""
         B, T, C, H, W = video.size()
-        slots, attns, _ = self.encode(video)
+        slots = self._slot_attns(video)[0]          # encode()'s slots and its draw, without the overlays it would make
         return self.decode(slots.flatten(end_dim=1)).reshape(B, T, C, H, W)

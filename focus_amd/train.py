@@ -109,12 +109,14 @@ def train_iter(model, optimizer, loss_fun, inputs, labels, meta, cfg, mixup_fn=N
     return preds, labels, loss
 
 
-def slot_train_step(model, optimizer, video, global_step, cfg, noise=None, stats=None):
+def slot_train_step(model, optimizer, video, global_step, cfg, noise=None, stats=None, raw_attns=False):
     """One iteration of slot_train_epoch (tools/steve_train_net.py:57-126): schedules -> forward -> mse + cross_entropy ->
     NaN check -> zero_grad -> backward -> clip-norm -> step.  Returns (loss, mse, cross_entropy, recon, attns, tau).
     TRAIN.MIXED_PRECISION selects bf16 storage inside the model (no autocast / GradScaler: see the module docstring).
     `stats`: a meters.StepStats(device, ks=(), aux_names=("mse", "cross_entropy")); loss, mse and cross_entropy then go into
-    its device tables and the host NaN check is left to the next stats.read()."""
+    its device tables and the host NaN check is left to the next stats.read().
+    `raw_attns`: the forward runs with attns="raw", so `attns` is the slot update's attention [B,T,N,K] and the fp32 overlays
+    [B,T,K,C,H,W], which the loop looks at once per epoch, are not made; everything else is the same bits."""
     import math
     from .slowfast.models import optimizer as optim
     from .slowfast.utils import lr_policy as lrp
@@ -124,8 +126,10 @@ def slot_train_step(model, optimizer, video, global_step, cfg, noise=None, stats
     lr_warmup_factor_dec = lrp.linear_warmup(global_step, 0.0, 1.0, 0, so.WARMUP_STEPS)               # :75-80
     lr_decay_factor = math.exp(global_step / so.HALF_LIFE * math.log(0.5))                            # :82
     optim.set_slot_lr(optimizer, cfg, lr_decay_factor, lr_warmup_factor_enc, lr_warmup_factor_dec)    # :85-89
-    recon, cross_entropy, mse, attns = model(video, tau, cfg.SLOTS.HARD) if noise is None else \
-        model(video, tau, cfg.SLOTS.HARD, noise=noise)                                                # :98
+    kw = {} if noise is None else {"noise": noise}
+    if raw_attns:
+        kw["attns"] = "raw"
+    recon, cross_entropy, mse, attns = model(video, tau, cfg.SLOTS.HARD, **kw)                        # :98
     mse = mse.mean()                                                                                  # :101-102
     cross_entropy = cross_entropy.mean()
     loss = mse + cross_entropy                                                                        # :104
@@ -150,27 +154,89 @@ def slot_train_step(model, optimizer, video, global_step, cfg, noise=None, stats
     return loss, mse, cross_entropy, recon, attns, tau
 
 
+def _slot_model(model):
+    return model.module if hasattr(model, "module") else model          # DistributedDataParallel (:148)
+
+
+@torch.no_grad()
+def slot_recon_video(model, video, recon, attn, N=8):
+    """The picture of steve_train_net.py:147-150 / :415-422 from the last batch of a loop: the autoregressive generation of
+    video[:N] (reconstruct_autoregressive: cached keys and values on the decode kernel), then utils/slot_misc.visualize_slots
+    on the raw attention `attn` [B,T,He*We,K] -> uint8 frames [1,T,3,Hg,Wg], the bytes add_video would make of the reference's
+    fp32 frames.  The generation runs in eval mode and the mode is put back afterwards: the reference generates in whatever
+    mode the loop left, i.e. after training with the decoder's dropout live."""
+    from .slowfast.utils import slot_misc
+    m = _slot_model(model)
+    was_training = m.training
+    m.eval()
+    try:
+        gen_video = m.reconstruct_autoregressive(video[:N])
+    finally:
+        m.train(was_training)
+    He, We = m.slot_grid
+    return slot_misc.visualize_slots(video.contiguous(), recon.contiguous(), gen_video.contiguous(), attn.contiguous(),
+                                     (He, We), N=N, out_dtype=torch.uint8)
+
+
 def slot_train_epoch(train_loader, model, optimizer, scaler, train_meter, cur_epoch, cfg, writer=None):
     """tools/steve_train_net.py:33-160 with the reference's argument list (scaler and train_meter are accepted and unused:
     bf16 needs no loss scaling, and the reference never touches the meter either).  `train_loader` yields video tensors
     [B,T,C,H,W]; `writer`, if given, receives the same scalar dict through add_scalars(dict, global_step=...).
-    Returns {'tau', 'global_step'} like the reference (:153-158).  The end-of-epoch autoregressive visualisation
-    (:146-150, slot_misc.visualize + add_video) is dataset/tensorboard plumbing and is not part of this path."""
+    Returns {'tau', 'global_step'} like the reference (:153-158).  The steps run with raw_attns=True: the overlays are
+    not made per step.  At the end of the epoch (:146-150) a writer that has add_video receives slot_recon_video of the last
+    batch -- uint8 frames where the reference hands over fp32 ones that TensorBoard converts -- under
+    tag='TRAIN_recons/epoch=%d' % (cur_epoch + 1); a writer without add_video gets the scalars alone."""
     model.train()
     data_size = len(train_loader)
     tau, global_step = None, cur_epoch * data_size
+    video = recon = attn = None
     for cur_iter, video in enumerate(train_loader):
         global_step = cur_epoch * data_size + cur_iter
         if cfg.NUM_GPUS:
             video = video.cuda(non_blocking=True)
-        loss, mse, ce, _recon, _attns, tau = slot_train_step(model, optimizer, video, global_step, cfg)
+        loss, mse, ce, recon, attn, tau = slot_train_step(model, optimizer, video, global_step, cfg, raw_attns=True)
+        recon = recon.detach()                                    # kept for the picture: not the step's autograd graph
         if writer is not None:
             with torch.no_grad():
                 writer.add_scalars({"TRAIN/loss": loss.item(), "TRAIN/cross_entropy": ce.item(), "TRAIN/mse": mse.item(),
                                     "TRAIN/tau": tau, "TRAIN/lr_dvae": optimizer.param_groups[0]["lr"],
                                     "TRAIN/lr_enc": optimizer.param_groups[1]["lr"],
                                     "TRAIN/lr_dec": optimizer.param_groups[2]["lr"]}, global_step=global_step)
+    if video is not None and hasattr(writer, "add_video"):                                            # :146-150
+        frames = slot_recon_video(model, video, recon, attn)
+        writer.add_video(frames, tag="TRAIN_recons/epoch=%d" % (cur_epoch + 1), global_step=cur_epoch + 1)
     return {"tau": tau, "global_step": global_step}
+
+
+@torch.no_grad()
+def slot_val_epoch(val_loader, model, cur_epoch, cfg, opd, writer=None):
+    """The STEVE validation loop (tools/steve_train_net.py:161-212, eval_epoch there): eval mode, no gradients, every batch
+    of `val_loader` (video tensors [B,T,C,H,W]) through the forward at opd['tau'].  The per-batch means of mse and
+    cross_entropy go into a meters.StepStats on the device -- one launch per batch where the reference makes two .item()
+    round trips -- and are read once at the end: val_loss = mean(mse) + mean(cross_entropy) over the batches, the double
+    sums of the reference's MetricTracker.  Returns (val_loss, {'video', 'recon', 'attns'}) of the last batch, with the raw
+    attention [B,T,N,K] for `attns` (slot_recon_video draws the VAL_recons picture of :415-422 from it); `writer`, if given,
+    receives VAL/loss, VAL/cross_entropy and VAL/mse through add_scalars(dict, global_step=cur_epoch + 1).  A NaN loss
+    raises at the read, as in the training loop (the reference returns the NaN)."""
+    from .slowfast.utils import meters
+    model.eval()
+    dev = next(model.parameters()).device
+    stats = video = recon = attns = None
+    for video in val_loader:
+        video = video.to(dev, non_blocking=True) if cfg.NUM_GPUS else video
+        recon, cross_entropy, mse, attns = model(video, opd["tau"], cfg.SLOTS.HARD, attns="raw")      # :186
+        mse, cross_entropy = mse.mean(), cross_entropy.mean()                                         # :189-190
+        if stats is None:
+            stats = meters.StepStats(video.device, ks=(), aux_names=("mse", "cross_entropy"))
+        stats.update(None, None, mse + cross_entropy, (mse, cross_entropy), batch=video.shape[0])
+    if stats is None:
+        raise ValueError("slot_val_epoch: the loader is empty")
+    fig = stats.read(reduce=False)                                # the reference averages per rank: no collective here
+    val_loss = fig["mse"] + fig["cross_entropy"]                                                      # :197
+    if writer is not None:
+        writer.add_scalars({"VAL/loss": val_loss, "VAL/cross_entropy": fig["cross_entropy"], "VAL/mse": fig["mse"]},
+                           global_step=cur_epoch + 1)                                                 # :204-208
+    return val_loss, {"video": video, "recon": recon, "attns": attns}
 
 
 @torch.no_grad()

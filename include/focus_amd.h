@@ -967,6 +967,43 @@ int focus_random_erase(void* x, int dtype, int B, int T, int C, int H, int W, in
                        const focus_erase_item* items, int n_items, int max_per_clip, int mode, const void* seed,
                        void* stream);
 
+/* -------------------------------------------------------------------------------------------------
+ * STEVE epoch visualisation (slot_vis.hip; slowfast/utils/slot_misc.py:16-35 of the reference): the video that
+ * visualize() hands to add_video -- per frame torch.cat((video, recon_dvae, recon_tf, attns)) put through torchvision's
+ * make_grid(tiles, nrow = K + 3, padding = 2, pad_value = 0.8) -- written whole in ONE launch.
+ *
+ * out [T,3,Hg,Wg] dense, Hg = rows (H + 2) + 2, Wg = (K + 3) (W + 2) + 2.  The canvas is 0.8f; tile (r, j) of frame t lies
+ * at rows r (H + 2) + 2 ... + H and columns j (W + 2) + 2 ... + W, for r < rows and j < K + 3:
+ *     j = 0: video[r,t]    j = 1: recon[r,t]    j = 2: gen[r,t]    j = 3 + k: the overlay of slot k.
+ * video [B,T,3,H,W], recon [B,T,3,H,W], gen [Bg,T,3,H,W]: dense, each FOCUS_F32 or FOCUS_BF16 by its own dtype argument
+ * (bf16 widens exactly, which is what torch.cat's type promotion does).  `slots` is the slot source, by slot_form:
+ *   FOCUS_SLOT_FORM_VIS  attns_vis [B,T,K,3,H,W] fp32, as STEVE.forward / encode return it; the tiles are copied.  He and We
+ *                        are not looked at.
+ *   FOCUS_SLOT_FORM_RAW  attn [B,T,He We,K] fp32 or bf16, as the slot update leaves it (K innermost), He | H and We | W.
+ *                        With sy = H / He, sx = W / We, v = video[r,t,c,y,x] and a = attn[r,t,(y / sy) We + x / sx,k], the
+ *                        pixel is  fadd(fmul(v, a), fsub(1, a))  in fp32, each of the three rounded on its own -- the
+ *                        bits of steve.py:314-319 (nearest upsampling by repeat_interleave, then mul, rsub, add) without
+ *                        any [B,T,K,...] tensor.  No FMA: a single rounding changes about one result in ten.
+ * out_type FOCUS_VIS_OUT_F32 writes those fp32 values: bit-equal to the reference's composition.  FOCUS_VIS_OUT_U8 writes
+ * what torch.utils.tensorboard (summary.py:video) makes of them on the host, (x * 255).clip(0, 255).astype(uint8) with the
+ * product rounded to fp32: the conversion TRUNCATES, a NaN becomes 0, the canvas comes out as 204.
+ *
+ * The launch is driven from the output: every element of out is written exactly once (vector stores in the aligned body of
+ * a canvas row, element stores at its two ends -- Wg is rarely a multiple of 4), nothing outside out is written, nothing
+ * is read but the tiles.  No workspace, no atomics: the same arguments give the same bits.
+ *
+ * Status, judged in this order before any launch (a refused call writes nothing): FOCUS_ERR_NULL (video, recon, gen, slots
+ * or out is NULL); FOCUS_ERR_SHAPE (an unknown slot_form; C != 3; K outside 1..32; B, Bg, H or W < 1; T < 0; rows < 0 or
+ * rows > min(B, Bg); in the raw form He or We < 1, H % He != 0 or W % We != 0; T 3 Hg Wg >= 2^31); FOCUS_ERR_DTYPE (a source
+ * neither FOCUS_F32 nor FOCUS_BF16; attns_vis not FOCUS_F32; an unknown out_type); FOCUS_ERR_ALIGN (a source, or an fp32
+ * out, not aligned to its element size); FOCUS_OK without a launch for rows == 0 or T == 0.
+ * ----------------------------------------------------------------------------------------------*/
+enum focus_slot_form { FOCUS_SLOT_FORM_VIS = 0, FOCUS_SLOT_FORM_RAW = 1 };
+enum focus_vis_out { FOCUS_VIS_OUT_F32 = 0, FOCUS_VIS_OUT_U8 = 1 };
+int focus_slot_vis_grid(const void* video, int dtype_video, const void* recon, int dtype_recon, const void* gen,
+                        int dtype_gen, const void* slots, int dtype_slots, int slot_form, int B, int Bg, int T, int C, int H,
+                        int W, int K, int He, int We, int rows, void* out, int out_type, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
