@@ -3518,3 +3518,131 @@ def view_accumulate(preds, clip_ids, labels, num_clips, video_preds, video_label
         _lib.check(_lib.lib().focus_view_accumulate(_p(preds), _dt(preds), n, C, preds.stride(0) if n > 1 else C, _p(clip_ids),
                                                     _p(labels), int(num_clips), NV, VIEW_MODES[mode], _p(video_preds),
                                                     _p(video_labels), _p(clip_count), _p(flag), _stream()), "view_accumulate")
+
+
+# --------------------------------------------------------------------------------------------------
+# The multi-label route (csrc/multilabel.hip): BCE losses, the dense view table, average precision
+# --------------------------------------------------------------------------------------------------
+BCE_MODES = {"logits": 0, "probs": 1}                                      # enum focus_bce_mode
+
+
+class _BceRowsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, mode, mean):
+        R, C = x.shape
+        xf = x.float()
+        if xf.stride(1) != 1:
+            xf = xf.contiguous()
+        loss_rows = torch.empty(R, device=x.device, dtype=torch.float32)
+        dx = torch.empty((R, C), device=x.device, dtype=torch.float32)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().focus_bce_rows(_p(xf), xf.stride(0) if R > 1 else C, _p(y), y.stride(0) if R > 1 else C, R, C,
+                                                 BCE_MODES[mode], 1.0 / (R * C) if mean else 1.0, _p(loss_rows), _p(dx), C,
+                                                 _stream()), "bce_rows")
+        ctx.save_for_backward(dx)
+        ctx.dtype = x.dtype
+        total = loss_rows.sum()                                 # R values; the rows themselves were summed in a fixed order
+        return total / (R * C) if mean else total
+
+    @staticmethod
+    def backward(ctx, g):
+        (dx,) = ctx.saved_tensors                   # d(mean or sum) / dx
+        return (dx * g.float()).to(ctx.dtype), None, None, None
+
+
+def _bce(x, y, reduction, mode, what):
+    _need_gpu(x, y)
+    if reduction not in ("mean", "sum"):
+        raise NotImplementedError("focus_amd: %s reduction is 'mean' or 'sum' (got %r); the train loops use no other" % (
+            what, reduction))
+    if x.dim() != 2 or x.shape != y.shape or x.numel() == 0 or y.device != x.device:
+        raise ValueError("focus_amd: %s takes inputs and targets of one [R,C] shape on one device (got %s on %s and %s on %s)" % (
+            what, tuple(x.shape), x.device, tuple(y.shape), y.device))
+    _dt(x)
+    y = y.detach().float()
+    if y.stride(1) != 1:
+        y = y.contiguous()
+    return _BceRowsFn.apply(x, y, mode, reduction == "mean")
+
+
+def bce_with_logits(x, y, reduction="mean"):
+    """nn.BCEWithLogitsLoss: max(x,0) - x y + log1p(exp(-|x|)) summed or averaged over all elements, value and gradient
+    (sigmoid(x) - y) from one row kernel.  x [R,C] fp32 or bf16 (widened first; the gradient comes back in x's type), y
+    [R,C] targets in [0,1] (used as fp32; no gradient flows into them).  A row stride is passed as it is."""
+    return _bce(x, y, reduction, "logits", "bce_with_logits")
+
+
+def bce(p, y, reduction="mean"):
+    """nn.BCELoss on probabilities p [R,C] in [0,1], with ATen's clamps: the logs at -100, the gradient's denominator at
+    1e-12.  Values outside [0,1], for which torch raises, give NaN: a check would cost a sync."""
+    return _bce(p, y, reduction, "probs", "bce")
+
+
+def view_accumulate_dense(preds, clip_ids, labels, num_clips, video_preds, video_labels, clip_count, flag, mode="sum"):
+    """view_accumulate for multi-label videos: labels are dense float32 rows [n,C] (a row stride is passed as it is),
+    video_labels is float32 [num_videos,C].  flag bit 0: the row stored for a video had a positive entry and a clip of that
+    video came with another row; bit 1: a clip id out of range.  One launch, no sync, no CPU fallback."""
+    _need_gpu(preds, clip_ids, labels, video_preds, video_labels, clip_count, flag)
+    if mode not in VIEW_MODES:
+        raise ValueError("focus_amd: view_accumulate_dense's mode is 'sum' or 'max'; got %r" % (mode,))
+    if preds.dim() != 2 or preds.dtype not in (torch.float32, torch.bfloat16) or preds.stride(1) != 1:
+        raise ValueError("focus_amd: view_accumulate_dense takes float32 or bfloat16 preds [n,C] with unit column stride; got %s %s "
+                         "with strides %s" % (preds.dtype, tuple(preds.shape), tuple(preds.stride())))
+    n, C = preds.shape
+    if clip_ids.dtype != torch.int64 or tuple(clip_ids.shape) != (n,) or not clip_ids.is_contiguous():
+        raise ValueError("focus_amd: view_accumulate_dense takes contiguous int64 clip_ids [%d]; got %s %s" % (
+            n, clip_ids.dtype, tuple(clip_ids.shape)))
+    if labels.dtype != torch.float32 or tuple(labels.shape) != (n, C) or labels.stride(1) != 1:
+        raise ValueError("focus_amd: view_accumulate_dense takes float32 labels [%d,%d] with unit column stride; got %s %s with "
+                         "strides %s" % (n, C, labels.dtype, tuple(labels.shape), tuple(labels.stride())))
+    for t, what in ((video_preds, "video_preds"), (video_labels, "video_labels")):
+        if t.dim() != 2 or t.shape[1] != C or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("focus_amd: view_accumulate_dense takes a contiguous float32 %s [num_videos,%d]; got %s %s" % (
+                what, C, t.dtype, tuple(t.shape)))
+    NV = video_preds.shape[0]
+    if video_labels.shape[0] != NV or clip_count.dtype != torch.int64 or tuple(clip_count.shape) != (NV,) \
+            or not clip_count.is_contiguous():
+        raise ValueError("focus_amd: view_accumulate_dense takes video_labels [%d,%d] and contiguous int64 clip_count [%d]; got %s "
+                         "and %s %s" % (NV, C, NV, tuple(video_labels.shape), clip_count.dtype, tuple(clip_count.shape)))
+    if flag.dtype != torch.int32 or flag.numel() != 1 or int(num_clips) < 1 or C < 1:
+        raise ValueError("focus_amd: view_accumulate_dense takes an int32 flag of one element, num_clips >= 1 and C >= 1; got %s "
+                         "%s, %s, %d" % (flag.dtype, tuple(flag.shape), num_clips, C))
+    with torch.cuda.device(preds.device):
+        _lib.check(_lib.lib().focus_view_accumulate_dense(
+            _p(preds), _dt(preds), n, C, preds.stride(0) if n > 1 else C, _p(clip_ids), _p(labels), labels.stride(0) if n > 1 else C,
+            int(num_clips), NV, VIEW_MODES[mode], _p(video_preds), _p(video_labels), _p(clip_count), _p(flag), _stream()),
+            "view_accumulate_dense")
+
+
+AP_BAD_LABEL, AP_BAD_SCORE, AP_NO_CLASS = 1, 2, 4                          # the bits of focus_average_precision's flag
+
+
+def average_precision(scores, labels):
+    """scikit-learn's average_precision_score(labels, scores, average=None) over the columns of a device table, by counting
+    (include/focus_amd.h): scores and labels float32 [N,C], labels 0 or 1, row strides passed as they are.  Returns
+    (ap float64 [C], npos int64 [C], summary float64 [2] = (mean ap over the classes with a positive, their number), flag
+    int32 [1]: AP_BAD_LABEL | AP_BAD_SCORE | AP_NO_CLASS).  Classes without a positive have ap 0 and are left out of the
+    mean.  Nothing is synchronised and nothing is read back here; no CPU fallback."""
+    _need_gpu(scores, labels)
+    if scores.dim() != 2 or scores.shape != labels.shape or scores.dtype != torch.float32 or labels.dtype != torch.float32 \
+            or scores.stride(1) != 1 or labels.stride(1) != 1 or scores.shape[1] < 1 or labels.device != scores.device:
+        raise ValueError("focus_amd: average_precision takes float32 scores and labels of one [N,C] shape, C >= 1, with unit column "
+                         "stride on one device; got %s %s %s on %s and %s %s %s on %s" % (
+                             scores.dtype, tuple(scores.shape), tuple(scores.stride()), scores.device, labels.dtype,
+                             tuple(labels.shape), tuple(labels.stride()), labels.device))
+    N, C = scores.shape
+    dev = scores.device
+    ap = torch.zeros(C, dtype=torch.float64, device=dev)
+    npos = torch.zeros(C, dtype=torch.int64, device=dev)
+    summary = torch.zeros(2, dtype=torch.float64, device=dev)
+    flag = torch.full((1,), AP_NO_CLASS, dtype=torch.int32, device=dev)     # what an empty table is left with
+    if N == 0:
+        return ap, npos, summary, flag
+    L = _lib.lib()
+    nbytes = L.focus_average_precision_workspace_bytes(N, C)
+    ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.focus_average_precision(_p(scores), scores.stride(0) if N > 1 else C, _p(labels),
+                                             labels.stride(0) if N > 1 else C, N, C, _p(npos), _p(ap), _p(summary), _p(flag),
+                                             _p(ws), nbytes, _stream()), "average_precision")
+    return ap, npos, summary, flag

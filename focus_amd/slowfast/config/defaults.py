@@ -132,7 +132,9 @@ def _defaults():
                         ATTN_LAYER="trajectory", APPROX_ATTN_TYPE="none", APPROX_ATTN_DIM=128))
     C.DATA = CfgNode(dict(PATH_TO_DATA_DIR="", PATH_PREFIX="", NUM_FRAMES=8, SAMPLING_RATE=8, MEAN=[0.45, 0.45, 0.45],
                           INPUT_CHANNEL_NUM=[3, 3], STD=[0.225, 0.225, 0.225], TRAIN_JITTER_SCALES=[256, 320],
-                          TRAIN_CROP_SIZE=224, TEST_CROP_SIZE=256, RANDOM_FLIP=True, REVERSE_INPUT_CHANNEL=False))
+                          TRAIN_CROP_SIZE=224, TEST_CROP_SIZE=256, RANDOM_FLIP=True, REVERSE_INPUT_CHANNEL=False,
+                          # the multi-label route (defaults.py:679-682 of the reference): BCE losses, mAP, "sum" / "max" views
+                          MULTI_LABEL=False, ENSEMBLE_METHOD="sum"))
     C.SLOTS_OPTIM = CfgNode(dict(DVAE=3e-4, ENC=1e-4, DEC=4e-4, HALF_LIFE=100000, WARMUP_STEPS=20000, CLIP=1.0,
                                  TAU_START=1.0, TAU_FINAL=0.1, TAU_STEPS=30000, STEPS=200000, STEP_INTERVAL=5000))
     C.SOLVER = CfgNode(dict(BASE_LR=0.1, ORVIT_BASE_LR=-1.0, LR_POLICY="cosine", COSINE_END_LR=0.0, GAMMA=0.1,

@@ -69,3 +69,16 @@ def boxes_to_orvit_format(boxes, height, width):
     boxes = torch.from_numpy(boxes)
     boxes = box_ops.box_xyxy_to_cxcywh(boxes)
     return box_ops.zero_empty_boxes(boxes, mode="cxcywh")
+
+
+def as_binary_vector(labels, num_classes):
+    """utils.py:190-203: a list of label indices -> the multi-hot float64 vector [num_classes] (duplicates count once)."""
+    label_arr = np.zeros((num_classes,))
+    for lbl in set(labels):
+        label_arr[lbl] = 1.0
+    return label_arr
+
+
+def aggregate_labels(label_list):
+    """utils.py:206-218: the union of a list of label lists, each label once (the order is a set's: unspecified)."""
+    return list({l for labels in label_list for l in labels})

@@ -1,6 +1,7 @@
 """Loss lookup (mirror of slowfast/models/losses.py:15-121): label-smoothing / plain cross entropy on the fused
 focus_xent_ls kernel, soft-target cross entropy (mixup / cutmix targets) on focus_xent_soft, and the EPIC-Kitchens
-verb+noun wrapper (EKLoss, losses.py:62-95)."""
+verb+noun wrapper (EKLoss, losses.py:62-95), and the two binary cross entropies of the multi-label route ("bce",
+"bce_logit": losses.py:91-92) on focus_bce_rows."""
 from functools import partial
 
 import torch.nn as nn
@@ -35,6 +36,32 @@ class LabelSmoothingCrossEntropy(nn.Module):
         return ops.label_smoothing_ce(x, target, self.smoothing)
 
 
+class BCEWithLogitsLoss(nn.Module):
+    """nn.BCEWithLogitsLoss (losses.py:92, "bce_logit") against multi-hot or soft targets [B,C]; reduction "mean" or "sum"."""
+
+    def __init__(self, reduction="mean"):
+        super().__init__()
+        if reduction not in ("mean", "sum"):
+            raise NotImplementedError("BCEWithLogitsLoss reduction=%r is not used by the train loops ('mean' or 'sum')" % reduction)
+        self.reduction = reduction
+
+    def forward(self, x, y):
+        return ops.bce_with_logits(x, y, self.reduction)
+
+
+class BCELoss(nn.Module):
+    """nn.BCELoss (losses.py:91, "bce") on probabilities, e.g. a head with MODEL.HEAD_ACT sigmoid; reduction "mean" or "sum"."""
+
+    def __init__(self, reduction="mean"):
+        super().__init__()
+        if reduction not in ("mean", "sum"):
+            raise NotImplementedError("BCELoss reduction=%r is not used by the train loops ('mean' or 'sum')" % reduction)
+        self.reduction = reduction
+
+    def forward(self, p, y):
+        return ops.bce(p, y, self.reduction)
+
+
 class EKLoss(nn.Module):
     """losses.py:62-95: {'verb_loss', 'noun_loss'} from the two heads' logits and a {'verb','noun'} label dict."""
 
@@ -55,7 +82,9 @@ class EKLoss(nn.Module):
 
 _LOSSES = {"cross_entropy": partial(LabelSmoothingCrossEntropy, smoothing=0.0),
            "soft_cross_entropy": SoftTargetCrossEntropy,
-           "label_smoothing_cross_entropy": LabelSmoothingCrossEntropy}
+           "label_smoothing_cross_entropy": LabelSmoothingCrossEntropy,
+           "bce": BCELoss,
+           "bce_logit": BCEWithLogitsLoss}
 
 
 def get_loss_func(cfg, state="train"):

@@ -1,33 +1,100 @@
 """Multi-view test ensembling (mirror of the arithmetic of slowfast/utils/meters.py:235-410 `TestMeter`; its timers and
 JSON logging are plumbing and are not reproduced).  Every video is sampled as NUM_ENSEMBLE_VIEWS x NUM_SPATIAL_CROPS
 clips; clip i belongs to video i // num_clips; predictions are summed (or max-ed) per video and top-k accuracy is
-taken over the videos."""
+taken over the videos.  With multi_label=True the labels are multi-hot rows and the metric is get_map (meters.py:1275-1299):
+the mean over the classes of scikit-learn's average precision."""
+import numpy as np
 import torch
 
 from . import metrics
 
 
+def _average_precision_columns(scores, labels):
+    """sklearn.metrics.average_precision_score(labels, scores, average=None) for binary columns, restated in numpy with
+    scikit-learn's own arithmetic (_binary_clf_curve, precision_recall_curve, average_precision_score): per class a stable
+    descending sort, one threshold per distinct score, AP = sum over thresholds of (recall step) x precision."""
+    aps = np.zeros(scores.shape[1], dtype=np.float64)
+    for c in range(scores.shape[1]):
+        order = np.argsort(scores[:, c], kind="mergesort")[::-1]
+        s, y = scores[order, c], labels[order, c] == 1
+        idx = np.r_[np.where(np.diff(s))[0], y.size - 1]
+        tps = np.cumsum(y, dtype=np.float64)[idx]
+        fps = 1 + idx - tps
+        ps = tps + fps
+        precision = np.zeros_like(tps)
+        np.divide(tps, ps, out=precision, where=(ps != 0))
+        recall = tps / tps[-1]
+        precision, recall = np.hstack((precision[::-1], 1)), np.hstack((recall[::-1], 0))
+        aps[c] = max(0.0, -np.sum(np.diff(recall) * precision[:-1]))
+    return aps
+
+
+def get_map(preds, labels):
+    """meters.py:1275-1299: the mean average precision over the classes that have a positive; 0.0 where scikit-learn raises
+    and the reference falls into its `except` (a score that is not finite, no class with a positive, an empty table).
+    numpy arrays and CPU tensors are scored here on the host, without scikit-learn; tensors on the device by one
+    focus_average_precision call and one small copy.  Labels other than 0 / 1 in a kept class raise ValueError: what
+    scikit-learn makes of them depends on its version."""
+    if isinstance(preds, torch.Tensor) and preds.is_cuda:
+        from focus_amd import ops
+        _, _, summary, flag = ops.average_precision(preds.detach().float(), labels.detach().to(preds.device, torch.float32))
+        t = torch.cat([summary, flag.double()]).cpu()                         # the one copy to the host
+        return _map_from(float(t[0]), int(t[2]))
+    preds = preds.detach().numpy() if isinstance(preds, torch.Tensor) else np.asarray(preds)
+    labels = labels.detach().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
+    keep = ~np.all(labels == 0, axis=0)
+    preds, labels = preds[:, keep], labels[:, keep]
+    if not np.all((labels == 0) | (labels == 1)):
+        raise ValueError("get_map: labels are 0 or 1")
+    if preds.shape[0] == 0 or preds.shape[1] == 0 or not np.all(np.isfinite(preds)):
+        return np.mean([0])                                                    # the reference's `except ValueError` path
+    return np.mean(_average_precision_columns(preds, labels))
+
+
+def _map_from(mean_ap, flag):
+    if flag & 1:
+        raise ValueError("get_map: labels are 0 or 1")
+    return np.mean([0]) if flag & 6 else np.float64(mean_ap)
+
+
 class TestMeter(object):
     def __init__(self, num_videos, num_clips, num_cls, overall_iters, multi_label=False, ensemble_method="sum"):
-        if multi_label:
-            raise NotImplementedError("multi-label mAP (meters.py:385-389) belongs to the AVA/Charades families")
         if ensemble_method not in ("sum", "max"):
             raise NotImplementedError("Ensemble Method {} is not supported".format(ensemble_method))
         self.num_clips = num_clips
         self.overall_iters = overall_iters
+        self.multi_label = multi_label
         self.ensemble_method = ensemble_method
         self.video_preds = torch.zeros((num_videos, num_cls))
-        self.video_labels = torch.zeros((num_videos)).long()
+        if multi_label:
+            self.video_preds -= 1e10                            # meters.py:276-277
+        self.video_labels = torch.zeros((num_videos, num_cls)) if multi_label else torch.zeros((num_videos)).long()
         self.clip_count = torch.zeros((num_videos)).long()
         self.stats = {}
 
     def reset(self):
         self.clip_count.zero_()
         self.video_preds.zero_()
+        if self.multi_label:
+            self.video_preds -= 1e10
         self.video_labels.zero_()
 
     def update_stats(self, preds, labels, clip_ids):
-        """meters.py:300-332, vectorised: one index_add_ / index_reduce_ per batch instead of a Python loop per clip."""
+        """meters.py:300-332, vectorised: one index_add_ / index_reduce_ per batch instead of a Python loop per clip.  The
+        multi-label form keeps the reference's loop: its table starts at -1e10, where the order of the fp32 sums shows."""
+        if self.multi_label:
+            preds, labels = preds.detach().float().cpu(), labels.detach().float().cpu()
+            for ind, cid in enumerate(clip_ids.detach().cpu().tolist()):
+                vid_id = int(cid) // self.num_clips
+                if self.video_labels[vid_id].sum() > 0:
+                    assert torch.equal(self.video_labels[vid_id], labels[ind]), "clips of one video disagree on its labels"
+                self.video_labels[vid_id] = labels[ind]
+                if self.ensemble_method == "sum":
+                    self.video_preds[vid_id] += preds[ind]
+                else:
+                    self.video_preds[vid_id] = torch.max(self.video_preds[vid_id], preds[ind])
+                self.clip_count[vid_id] += 1
+            return
         preds, labels = preds.detach().float().cpu(), labels.detach().cpu().long()
         vid = (clip_ids.detach().cpu().long() // self.num_clips)
         seen = self.video_labels[vid] > 0
@@ -40,9 +107,12 @@ class TestMeter(object):
         self.clip_count.index_add_(0, vid, torch.ones_like(vid))
 
     def finalize_metrics(self, ks=(1, 5)):
-        """meters.py:372-410 -> {'split': 'test_final', 'top1_acc': 'xx.xx', ...}; `complete` says whether every video
-        received exactly num_clips clips (the reference only logs a warning)."""
+        """meters.py:372-410 -> {'split': 'test_final', 'top1_acc': 'xx.xx', ...}, or with multi_label {'split', 'map'};
+        `complete` says whether every video received exactly num_clips clips (the reference only logs a warning)."""
         self.stats = {"split": "test_final", "complete": bool(torch.all(self.clip_count == self.num_clips))}
+        if self.multi_label:
+            self.stats["map"] = get_map(self.video_preds.cpu().numpy(), self.video_labels.cpu().numpy())
+            return self.stats
         correct = metrics.topks_correct(self.video_preds, self.video_labels, ks)
         for k, x in zip(ks, correct):
             self.stats["top{}_acc".format(k)] = "{:.{prec}f}".format(float(x / self.video_preds.size(0)) * 100.0, prec=2)
@@ -157,17 +227,23 @@ def _as_tuple(x):
 class DeviceTestMeter(object):
     """TestMeter with its tables on the device: `update_stats` is one focus_view_accumulate launch and no sync (CPU clip_ids
     and labels are copied non-blocking), `finalize_metrics` scores the table with focus_topk_stats.  The assertion
-    TestMeter makes per batch -- the clips of a video agree on its label -- is deferred to finalize_metrics."""
+    TestMeter makes per batch -- the clips of a video agree on its label -- is deferred to finalize_metrics.
+    multi_label=True: the label table is float32 [num_videos,num_cls], the score table starts at -1e10, `update_stats` is one
+    focus_view_accumulate_dense launch and `finalize_metrics` one focus_average_precision call and one copy -> 'map'."""
 
-    def __init__(self, num_videos, num_clips, num_cls, overall_iters, device, ensemble_method="sum"):
+    def __init__(self, num_videos, num_clips, num_cls, overall_iters, device, ensemble_method="sum", multi_label=False):
         if ensemble_method not in ("sum", "max"):
             raise NotImplementedError("Ensemble Method {} is not supported".format(ensemble_method))
         self.num_clips = num_clips
         self.overall_iters = overall_iters
         self.ensemble_method = ensemble_method
+        self.multi_label = bool(multi_label)
         self.device = torch.device(device)
         self.video_preds = torch.zeros((num_videos, num_cls), device=self.device)
-        self.video_labels = torch.zeros((num_videos), device=self.device).long()
+        if self.multi_label:
+            self.video_preds -= 1e10
+        self.video_labels = torch.zeros((num_videos, num_cls), device=self.device) if self.multi_label else \
+            torch.zeros((num_videos), device=self.device).long()
         self.clip_count = torch.zeros((num_videos), device=self.device).long()
         self.flag = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.stats = {}
@@ -175,11 +251,20 @@ class DeviceTestMeter(object):
     def reset(self):
         self.clip_count.zero_()
         self.video_preds.zero_()
+        if self.multi_label:
+            self.video_preds -= 1e10
         self.video_labels.zero_()
         self.flag.zero_()
 
     def update_stats(self, preds, labels, clip_ids):
         from focus_amd import ops
+        if self.multi_label:
+            labels = labels.detach().to(self.device, torch.float32, non_blocking=True)
+            clip_ids = clip_ids.detach().to(self.device, torch.int64, non_blocking=True).contiguous()
+            ops.view_accumulate_dense(preds.detach(), clip_ids, labels if labels.stride(-1) == 1 else labels.contiguous(),
+                                      self.num_clips, self.video_preds, self.video_labels, self.clip_count, self.flag,
+                                      self.ensemble_method)
+            return
         labels = labels.detach().to(self.device, torch.int64, non_blocking=True).contiguous()
         clip_ids = clip_ids.detach().to(self.device, torch.int64, non_blocking=True).contiguous()
         ops.view_accumulate(preds.detach(), clip_ids, labels, self.num_clips, self.video_preds, self.video_labels,
@@ -191,6 +276,13 @@ class DeviceTestMeter(object):
 
     def finalize_metrics(self, ks=(1, 5)):
         from focus_amd import ops
+        if self.multi_label:
+            _, _, summary, ap_flag = ops.average_precision(self.video_preds, self.video_labels)
+            complete = (self.clip_count == self.num_clips).all().double().reshape(1)
+            t = torch.cat([summary, ap_flag.double(), complete, self.flag.double()]).cpu()   # the one copy to the host
+            self._check_flag(int(t[4]))
+            self.stats = {"split": "test_final", "complete": bool(t[3]), "map": _map_from(float(t[0]), int(t[2]))}
+            return self.stats
         acc_i = torch.zeros(_NI, dtype=torch.int64, device=self.device)
         acc_f = torch.zeros(_NF, dtype=torch.float64, device=self.device)
         ops.topk_stats(acc_i, acc_f, self.video_preds, self.video_labels, ks)
@@ -203,6 +295,52 @@ class DeviceTestMeter(object):
             x = torch.tensor(float(t[_CORRECT + j]))                           # the fp32 count metrics.topks_correct returns
             self.stats["top{}_acc".format(k)] = "{:.{prec}f}".format(float(x / n) * 100.0, prec=2)
         return self.stats
+
+
+class MultiLabelStats(object):
+    """What ValMeter.update_predictions and the epoch-end get_map do under DATA.MULTI_LABEL (meters.py:694-747,
+    train_net.py:433-475), without the Python list of batches: `update` copies the batch into rows [offset, offset + n) of two
+    preallocated float32 tables [capacity,num_cls] -- the offset is known on the host, nothing synchronises -- and `read`
+    scores the filled part with get_map.  With several ranks `read` gathers the filled parts once; the reference gathers
+    every batch.  CPU tables take the numpy path of get_map."""
+
+    def __init__(self, device, num_cls, capacity):
+        self.device = torch.device(device)
+        self.preds = torch.empty((int(capacity), int(num_cls)), dtype=torch.float32, device=self.device)
+        self.labels = torch.empty((int(capacity), int(num_cls)), dtype=torch.float32, device=self.device)
+        self.offset = 0
+
+    def reset(self):
+        self.offset = 0
+
+    def update(self, preds, labels):
+        n = preds.shape[0]
+        if self.offset + n > self.preds.shape[0]:
+            raise RuntimeError("MultiLabelStats: %d rows do not fit behind %d of a capacity of %d" % (
+                n, self.offset, self.preds.shape[0]))
+        self.preds[self.offset:self.offset + n].copy_(preds.detach(), non_blocking=True)
+        self.labels[self.offset:self.offset + n].copy_(labels.detach(), non_blocking=True)
+        self.offset += n
+
+    def read(self, reset=True, reduce=True):
+        """{'map': get_map over the rows of all ranks, 'samples': their number}."""
+        preds, labels = self.preds[:self.offset], self.labels[:self.offset]
+        world = _distributed_world() if reduce else 1
+        if world > 1:
+            import torch.distributed as dist
+            counts = [torch.zeros(1, dtype=torch.int64, device=self.device) for _ in range(world)]
+            dist.all_gather(counts, torch.tensor([self.offset], dtype=torch.int64, device=self.device))
+            counts = [int(c) for c in torch.cat(counts).cpu()]
+            both = torch.zeros((max(counts), 2 * self.preds.shape[1]), dtype=torch.float32, device=self.device)
+            both[:self.offset] = torch.cat([preds, labels], dim=1)
+            parts = [torch.empty_like(both) for _ in range(world)]
+            dist.all_gather(parts, both)                                      # the one gather of the epoch
+            both = torch.cat([p[:c] for p, c in zip(parts, counts)])
+            preds, labels = both[:, :self.preds.shape[1]], both[:, self.preds.shape[1]:]
+        out = {"map": float(get_map(preds, labels)), "samples": int(preds.shape[0])}
+        if reset:
+            self.reset()
+        return out
 
 
 class EPICTestMeter(object):

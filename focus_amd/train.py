@@ -17,7 +17,9 @@ from .slowfast.utils import misc
 def train_step(model, optimizer, loss_fun, inputs, labels, meta, cfg, check_nan=True, stats=None):
     """`stats`: a meters.StepStats.  The step's loss (for epickitchens also verb_loss and noun_loss), the top-k counts and the
     NaN guard then go into its device tables by one launch right after the loss; the host NaN check is not made whatever
-    `check_nan` says, and a NaN surfaces at the next stats.read().  Labels may be the dense rows of mixup."""
+    `check_nan` says, and a NaN surfaces at the next stats.read().  Labels may be the dense rows of mixup.  Under
+    cfg.DATA.MULTI_LABEL the labels are multi-hot rows, which have no top-k: the loss and the NaN guard alone are kept
+    (train_net.py:234-238), the top-k columns stay zero."""
     preds = model(inputs, meta)                                   # train_net.py:86
     extra_preds = None
     if isinstance(preds, tuple):                                  # :87-88 (EK: (verb, {'verb','noun'}))
@@ -30,6 +32,8 @@ def train_step(model, optimizer, loss_fun, inputs, labels, meta, cfg, check_nan=
     if stats is not None:
         if cfg.TRAIN.DATASET == "epickitchens":
             stats.update(extra_preds, labels, loss, (loss_dict["verb_loss"], loss_dict["noun_loss"]))
+        elif cfg.DATA.MULTI_LABEL:
+            stats.update(None, None, loss, batch=preds.shape[0])
         else:
             stats.update(preds, labels, loss)
     elif check_nan:
@@ -278,10 +282,26 @@ def eval_epoch(val_loader, model, cfg, stats=None):
     """The validation loop (tools/train_net.py:311-470, the single-label and the epickitchens branch): eval mode, no
     gradients, `val_loader` yields (inputs, labels, _, meta).  Every batch is one meters.StepStats.update (made here when
     none is given) and nothing is read until the end: one read, then the epoch's figures -- top-k errors, or verb / noun /
-    action accuracies -- over all samples (and ranks) are returned."""
+    action accuracies -- over all samples (and ranks) are returned.
+    Under cfg.DATA.MULTI_LABEL (:433-435, :475 and meters.py:743-747) the predictions and the multi-hot labels of every batch
+    are copied into a meters.MultiLabelStats (`stats`, or one made here with room for len(val_loader.dataset) rows, else for
+    batches x the first batch's rows) and its read -- {'map', 'samples'} -- is returned: one gather and one
+    focus_average_precision call per epoch."""
     from .slowfast.utils import meters
     model.eval()
     dev = next(model.parameters()).device
+    if cfg.DATA.MULTI_LABEL:
+        for inputs, labels, _, meta in val_loader:
+            inputs = [x.to(dev) for x in inputs] if isinstance(inputs, (list, tuple)) else inputs.to(dev)
+            meta = {k: (v.to(dev) if isinstance(v, torch.Tensor) else v) for k, v in meta.items()}
+            preds = model(inputs, meta)
+            if isinstance(preds, tuple):
+                preds = preds[0]
+            if stats is None:
+                rows = len(val_loader.dataset) if hasattr(val_loader, "dataset") else len(val_loader) * preds.shape[0]
+                stats = meters.MultiLabelStats(dev, preds.shape[1], rows)
+            stats.update(preds, labels)
+        return stats.read() if stats is not None else {}
     ek = zero = None
     for inputs, labels, _, meta in val_loader:
         inputs = [x.to(dev) for x in inputs] if isinstance(inputs, (list, tuple)) else inputs.to(dev)

@@ -1004,6 +1004,62 @@ int focus_slot_vis_grid(const void* video, int dtype_video, const void* recon, i
                         int dtype_gen, const void* slots, int dtype_slots, int slot_form, int B, int Bg, int T, int C, int H,
                         int W, int K, int He, int We, int rows, void* out, int out_type, void* stream);
 
+/* -------------------------------------------------------------------------------------------------
+ * The multi-label route (multilabel.hip; DATA.MULTI_LABEL of the reference: slowfast/models/losses.py:91-92,
+ * slowfast/utils/meters.py:275-334, :390-394 and :1275-1299).  No float atomics and no data-dependent order in any of the
+ * three: the same arguments give the same bits.
+ *
+ * focus_bce_rows: nn.BCEWithLogitsLoss (FOCUS_BCE_LOGITS) and nn.BCELoss (FOCUS_BCE_PROBS), value and gradient in one launch.
+ *   x [R,C] fp32 with row stride ldx, targets y [R,C] fp32 with row stride ldy (any value in [0,1], not only 0 / 1).
+ *   loss_rows [R] fp32: the sum of the row's elements -- thread t of the row's 256-thread workgroup adds elements t, t + 256, ...
+ *   in ascending order, the 256 partial sums are folded by halving.  dx [R,C] fp32 with row stride lddx: grad_scale times the
+ *   derivative of that sum; the caller passes 1 / (R C) for the mean and 1 for the sum.  Per element, every operation in fp32:
+ *     logits  e = max(x, 0) - x y + log1pf(expf(-|x|))                      de/dx = sigmoid(x) - y, sigmoid from the same expf
+ *     probs   e = -(y max(logf(x), -100) + (1 - y) max(log1pf(-x), -100))   de/dx = (x - y) / max((1 - x) x, 1e-12f)
+ *   The second line is ATen's clamp rule.  expf, logf and log1pf are the accurate library functions.  Probabilities outside
+ *   [0,1] (ATen raises) give NaN.  Elements of x, y and dx past C in a row are neither read nor written.
+ *   Status, in this order, before any launch: FOCUS_ERR_NULL (any pointer); FOCUS_ERR_SHAPE (R < 0, C < 1, a row stride below C,
+ *     an unknown mode); FOCUS_OK without a launch for R == 0.
+ *
+ * focus_view_accumulate_dense: focus_view_accumulate for TestMeter(multi_label=True).  The same ownership rule (the rows of
+ *   a batch that share a video are folded in ascending row order by the first of them, starting from the table's row), the
+ *   same modes, clip_count and sticky flag (bit 1: a clip id outside [0, num_videos num_clips)).  What differs: labels is
+ *   dense fp32 [n,C] with row stride ldl and video_labels fp32 [num_videos,C]; walking its rows the owner sets bit 0 of
+ *   flag when the row stored for the video has an element > 0 (for labels >= 0: a sum > 0, the reference's test) and is not
+ *   element-wise equal to the clip's row; the clip's row is stored either way.  The table's first value is the caller's
+ *   business: the reference fills -1e10, and with FOCUS_VIEW_SUM fp32 then swallows every score added to it.
+ *   Status, before any launch: FOCUS_ERR_NULL (any pointer); FOCUS_ERR_SHAPE (num_clips < 1, num_videos < 0, C < 1, ld < C,
+ *     ldl < C, an unknown mode, C > 65535 * 256); FOCUS_ERR_DTYPE (preds neither fp32 nor bf16); FOCUS_OK without a launch
+ *     for n <= 0.
+ *
+ * focus_average_precision: get_map for a table on the device.  scores [N,C] fp32 with row stride lds, labels [N,C] fp32
+ *   with row stride ldl, 0 or 1.  For class c with positives P = {i : y_i == 1}, scikit-learn's step-wise average precision
+ *   (tied scores form one threshold) is
+ *       AP_c = (1 / |P|) sum_{i in P} TP_i / CNT_i,    CNT_i = #{j : s_j >= s_i},  TP_i = #{j : s_j >= s_i, y_j == 1}:
+ *   the threshold s_i contributes (its positives / |P|) x (its precision TP / CNT), once per positive at it.  The counts are
+ *   integers and exact; nothing is sorted.  Order of the double sum: rows in tiles of 256; per tile the 256 quotients (0 for
+ *   a row that is no positive) are folded by halving (slot s += slot s + h, h = 128, ..., 1), the tiles' sums are added in
+ *   ascending order, the total is divided by |P|.
+ *   npos [C] int64: the number of non-zero labels of the class (its positives, for 0 / 1 labels).  A class with npos == 0 is
+ *   left out, as get_map drops all-zero label columns, and gets ap 0.  ap [C] float64.  summary float64 [2]: the mean of
+ *   ap over the kept classes, added in ascending class order by one thread (0 when none is kept), and their number.
+ *   flag int32 [1], OVERWRITTEN: bit 0 a label of a kept class is neither 0 nor 1; bit 1 a score of a kept class is not
+ *   finite; bit 2 no class kept.  scikit-learn raises for bits 1 and 2, and get_map then returns 0.
+ *   workspace: focus_average_precision_workspace_bytes(N, C) bytes, 8-byte aligned; two launches on the caller's stream.
+ *   Status, in this order, before any launch: FOCUS_ERR_NULL (scores, labels, npos, ap, summary, flag); FOCUS_ERR_SHAPE
+ *     (N < 0, C < 1, C > 65535, a row stride below C, ceil(N / 256) C >= 2^23); FOCUS_OK without a launch, NOTHING written,
+ *     for N == 0; FOCUS_ERR_NULL (workspace); FOCUS_ERR_ALIGN; FOCUS_ERR_WORKSPACE.
+ * ----------------------------------------------------------------------------------------------*/
+enum focus_bce_mode { FOCUS_BCE_LOGITS = 0, FOCUS_BCE_PROBS = 1 };
+int focus_bce_rows(const float* x, int64_t ldx, const float* y, int64_t ldy, int R, int C, int mode, float grad_scale,
+                   float* loss_rows, float* dx, int64_t lddx, void* stream);
+int focus_view_accumulate_dense(const void* preds, int dtype, int n, int C, int64_t ld, const int64_t* clip_ids,
+                                const float* labels, int64_t ldl, int num_clips, int num_videos, int mode, float* video_preds,
+                                float* video_labels, int64_t* clip_count, int32_t* flag, void* stream);
+size_t focus_average_precision_workspace_bytes(int N, int C);
+int focus_average_precision(const float* scores, int64_t lds, const float* labels, int64_t ldl, int N, int C, int64_t* npos,
+                            double* ap, double* summary, int32_t* flag, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
