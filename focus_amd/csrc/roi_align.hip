@@ -4,54 +4,10 @@
 // HBM-bound: per output cell and channel, 4 gathered reads (L2-resident: a 14x14x768 map is 300 KB)
 // and one write.
 #include "focus_common.h"
+#include "roi_geometry.h"
 #include <cstdlib>
 
 namespace {
-
-struct Geom { float y1, x1, bin_h, bin_w; int grid_h, grid_w; float count; };
-struct Nbr { int y_low, x_low, y_high, x_high; float w1, w2, w3, w4; };
-
-__device__ __forceinline__ Geom roi_geometry(const float* roi, float scale, int PH, int PW, int sampling_ratio,
-                                             int aligned) {
-    Geom g;
-    const float off = aligned ? 0.5f : 0.0f;
-    g.x1 = __fsub_rn(__fmul_rn(roi[0], scale), off);
-    g.y1 = __fsub_rn(__fmul_rn(roi[1], scale), off);
-    const float x2 = __fsub_rn(__fmul_rn(roi[2], scale), off);
-    const float y2 = __fsub_rn(__fmul_rn(roi[3], scale), off);
-    float rw = __fsub_rn(x2, g.x1), rh = __fsub_rn(y2, g.y1);
-    if (!aligned) { if (rw < 1.0f) rw = 1.0f; if (rh < 1.0f) rh = 1.0f; }
-    g.bin_h = __fdiv_rn(rh, (float)PH);
-    g.bin_w = __fdiv_rn(rw, (float)PW);
-    g.grid_h = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(__fdiv_rn(rh, (float)PH));
-    g.grid_w = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(__fdiv_rn(rw, (float)PW));
-    const int c = g.grid_h * g.grid_w;
-    g.count = (float)(c > 1 ? c : 1);
-    return g;
-}
-__device__ __forceinline__ float sample_coord(float start, int p, float bin, int i, int grid) {
-    // start + p*bin + (i + 0.5)*bin/grid, evaluated left to right as in the oracle
-    return __fadd_rn(__fadd_rn(start, __fmul_rn((float)p, bin)),
-                     __fdiv_rn(__fmul_rn(__fadd_rn((float)i, 0.5f), bin), (float)grid));
-}
-__device__ __forceinline__ Nbr locate(float y, float x, int H, int W) {
-    Nbr n;
-    if (y < -1.0f || y > (float)H || x < -1.0f || x > (float)W) {
-        n.y_low = n.x_low = n.y_high = n.x_high = -1;
-        n.w1 = n.w2 = n.w3 = n.w4 = 0.f;
-        return n;
-    }
-    if (y <= 0.f) y = 0.f;
-    if (x <= 0.f) x = 0.f;
-    n.y_low = (int)y;
-    n.x_low = (int)x;
-    if (n.y_low >= H - 1) { n.y_high = n.y_low = H - 1; y = (float)n.y_low; } else n.y_high = n.y_low + 1;
-    if (n.x_low >= W - 1) { n.x_high = n.x_low = W - 1; x = (float)n.x_low; } else n.x_high = n.x_low + 1;
-    const float ly = __fsub_rn(y, (float)n.y_low), lx = __fsub_rn(x, (float)n.x_low);
-    const float hy = __fsub_rn(1.0f, ly), hx = __fsub_rn(1.0f, lx);
-    n.w1 = __fmul_rn(hy, hx); n.w2 = __fmul_rn(hy, lx); n.w3 = __fmul_rn(ly, hx); n.w4 = __fmul_rn(ly, lx);
-    return n;
-}
 
 // grid: (PH, K); block 256 threads sweep (pw, channel-quad) of one output row of one RoI.
 template <typename T>

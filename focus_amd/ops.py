@@ -2049,6 +2049,68 @@ def cell_amax(x):
     return _CellAmaxFn.apply(x)
 
 
+class _RoiHeadPoolFn(torch.autograd.Function):
+    """max over bins of RoIAlign(mean over T) of the patch tokens of x [B, cls + T*H*W, C], read in place; the backward
+    returns a gradient of x's shape (cls rows zero).  rois [K,5] fp32 on the device."""
+
+    @staticmethod
+    def forward(ctx, x, rois, T, H, W, PH, PW, scale, sampling_ratio, aligned, cls):
+        _need_gpu(x, rois)
+        x = x.contiguous()
+        B, N, C = x.shape
+        if N != cls + T * H * W:
+            raise ValueError("roi_head_pool: x has %d tokens, cls + T*H*W = %d" % (N, cls + T * H * W))
+        K = rois.shape[0]
+        L = _lib.lib()
+        pooled = torch.empty(K, C, device=x.device, dtype=x.dtype)
+        arg = torch.empty(K, C, device=x.device, dtype=torch.int32)
+        nb = L.focus_roi_head_workspace_bytes(B, H, W, C)
+        ws = torch.empty(nb // 4, device=x.device, dtype=torch.float32)
+        _lib.check(L.focus_roi_head_fwd(_p(x, cls * C), N * C, _p(rois), _p(pooled), _p(arg), _p(ws), nb, B, T, H, W, C, K, PH,
+                                        PW, scale, sampling_ratio, int(aligned), _dt(x), _stream()), "roi_head_fwd")
+        ctx.save_for_backward(rois, arg)
+        ctx.args = (B, N, C, T, H, W, K, PH, PW, scale, sampling_ratio, int(aligned), cls, x.dtype)
+        ctx.mark_non_differentiable(arg)
+        return pooled, arg
+
+    @staticmethod
+    def backward(ctx, dpooled, _darg):
+        rois, arg = ctx.saved_tensors
+        B, N, C, T, H, W, K, PH, PW, scale, sr, al, cls, dt = ctx.args
+        dpooled = dpooled.contiguous().to(dt)
+        dx = torch.empty(B, N, C, device=dpooled.device, dtype=dt)
+        if cls:
+            dx[:, :cls].zero_()                                   # cls row: no box reads it
+        _lib.check(_lib.lib().focus_roi_head_bwd(_p(dpooled), _p(arg), _p(rois), _p(dx, cls * C), N * C, B, T, H, W, C, K, PH,
+                                                 PW, scale, sr, al, _dt(dx), _stream()), "roi_head_bwd")
+        return dx, None, None, None, None, None, None, None, None, None, None
+
+
+def roi_head_boxes(rois, B, device):
+    """rois [K,5] (batch index, x1, y1, x2, y2) as the fp32 device tensor the kernels read.  While the boxes are still a host
+    tensor (how a loader hands them over) their batch indices are checked here, without a sync: an index that is not an
+    integer in [0, B) is refused.  Boxes already on the device are taken as they are (the kernels skip such a box)."""
+    if rois.dim() != 2 or rois.shape[1] != 5:
+        raise ValueError("roi_head_pool: boxes must be [K,5] (batch index, x1, y1, x2, y2), got %s" % (tuple(rois.shape),))
+    if rois.device.type == "cpu":
+        idx = rois[:, 0]
+        if rois.shape[0] and not bool(((idx >= 0) & (idx < B) & (idx == idx.floor())).all()):
+            raise ValueError("roi_head_pool: box batch index outside [0, %d) (%s: %s)" % (
+                B, _lib.lib().focus_strerror(-1).decode(), idx.tolist()))
+        rois = rois.to(device=device, dtype=torch.float32, non_blocking=True)
+    return rois.float().contiguous()
+
+
+def roi_head_pool(x, rois, T, H, W, PH, PW, spatial_scale, sampling_ratio=0, aligned=True, cls=1, return_arg=False):
+    """ResNetRoIHead's pooling on the token stream: x [B, cls + T*H*W, C], rois [K,5] (batch index, x1, y1, x2, y2 in input
+    pixels) -> [K, C] = MaxPool2d(PH,PW)(ROIAlign(AvgPool3d([T,1,1])(x))) without the transpose and the [K,PH*PW,C]
+    intermediate (csrc/roi_head.hip).  spatial_scale multiplies the box coordinates (1 / SPATIAL_SCALE_FACTOR)."""
+    rois = roi_head_boxes(rois, x.shape[0], x.device)
+    pooled, arg = _RoiHeadPoolFn.apply(x, rois, int(T), int(H), int(W), int(PH), int(PW), float(spatial_scale),
+                                       int(sampling_ratio), bool(aligned), int(cls))
+    return (pooled, arg) if return_arg else pooled
+
+
 class _BoxLayoutFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, vecs, boxes, H, W):

@@ -148,7 +148,7 @@ def _defaults():
                           DROPPATH_RATE=0.1, DEPTH=16, NORM="layernorm", DIM_MUL=[], HEAD_MUL=[], POOL_KV_STRIDE=None,
                           POOL_KV_STRIDE_ADAPTIVE=None, POOL_Q_STRIDE=[], POOL_KVQ_KERNEL=None, ZERO_DECAY_POS_CLS=True,
                           NORM_STEM=False, SEP_POS_EMBED=False, DROPOUT_RATE=0.0, POOL_KV_IGNORE_111_KERNEL=False))
-    C.DETECTION = CfgNode(dict(ENABLE=False))
+    C.DETECTION = CfgNode(dict(ENABLE=False, ALIGNED=True, SPATIAL_SCALE_FACTOR=16, ROI_XFORM_RESOLUTION=7))
     C.DATA_LOADER = CfgNode(dict(NUM_WORKERS=8, PIN_MEMORY=True, ENABLE_MULTI_THREAD_DECODE=False))
     C.TENSORBOARD = CfgNode(dict(ENABLE=True))
     C.NUM_GPUS = 1

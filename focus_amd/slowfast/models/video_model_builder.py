@@ -222,20 +222,64 @@ class TransformerBasicHead(nn.Module):
         return x if self.training else self.act(x)
 
 
+class ResNetRoIHead(nn.Module):
+    """head_helper.py:11-130 on the token layout: temporal average, RoIAlign (sampling_ratio 0) and the max over its bins as
+    one pooling (ops.roi_head_pool, csrc/roi_head.hip), then (dropout,) Linear and the activation -- applied in training too,
+    as the reference does (:127-130).  Constructor arguments and state_dict keys (projection.weight, projection.bias; the
+    pools hold no parameters) are the reference's.  One pathway: the MViT route never builds more.
+    forward(inputs, bboxes, thw=None, cls=0): inputs = [tokens [B, cls + T*H*W, C]] (normalised, channels-last; the cls row is
+    skipped by addressing), bboxes [K,5] = (batch index, x1, y1, x2, y2) in input pixels."""
+
+    def __init__(self, dim_in, num_classes, pool_size, resolution, scale_factor, dropout_rate=0.0, act_func="softmax",
+                 aligned=True):
+        super().__init__()
+        assert len({len(pool_size), len(dim_in)}) == 1, "pathway dimensions are not consistent."
+        self.num_pathways = len(pool_size)
+        if self.num_pathways != 1:
+            raise NotImplementedError("ResNetRoIHead: one pathway (the MViT route); the SlowFast builders are out of scope")
+        self.pool_size = [list(p) for p in pool_size]
+        res = resolution[0]
+        self.resolution = [int(res[0]), int(res[1])] if isinstance(res, (list, tuple)) else [int(res)] * 2
+        self.spatial_scale = 1.0 / scale_factor[0]
+        self.aligned = bool(aligned)
+        self.dropout_rate = float(dropout_rate)
+        self.projection = nn.Linear(sum(dim_in), num_classes, bias=True)
+        if act_func == "softmax":
+            self.act = nn.Softmax(dim=1)
+        elif act_func == "sigmoid":
+            self.act = nn.Sigmoid()
+        else:
+            raise NotImplementedError("{} is not supported as an activation function.".format(act_func))
+
+    def forward(self, inputs, bboxes, thw=None, cls=0):
+        assert len(inputs) == self.num_pathways, "Input tensor does not contain {} pathway".format(self.num_pathways)
+        x = inputs[0]
+        if thw is None or x.dim() != 3:
+            raise ValueError("ResNetRoIHead takes the token tensor [B, cls + T*H*W, C] and thw, not a [B,C,T,H,W] map")
+        T, H, W = thw
+        if T != self.pool_size[0][0]:                             # the reference: assert out.shape[2] == 1 after the pool
+            raise ValueError("ResNetRoIHead: %d frames reach a temporal pool of %d" % (T, self.pool_size[0][0]))
+        x = ops.roi_head_pool(x, bboxes, T, H, W, self.resolution[0], self.resolution[1], self.spatial_scale,
+                              sampling_ratio=0, aligned=self.aligned, cls=cls)
+        if self.dropout_rate > 0.0:
+            x = ops.dropout_add(x, None, self.dropout_rate, self.training)
+        x = ops.linear(x, self.projection.weight, self.projection.bias).float()
+        return self.act(x)
+
+
 @MODEL_REGISTRY.register()
 class MViT(nn.Module):
     """Multiscale Vision Transformer with ORViT blocks (video_model_builder.py:765-1101): an ORViT block takes the place of
     the MultiScaleBlock at the layers in ORVIT.LAYERS (:915-928) or runs beside it at the layers in ORVIT.ADD_LAYERS, its
-    output added to the block's (:952-972, :1077-1082).  The detection head (:975-986, RoI head over AVA boxes) is not part
-    of this path."""
+    output added to the block's (:952-972, :1077-1082).  Under DETECTION.ENABLE the head is the RoI head over AVA boxes
+    (:978-988, :1085-1092): forward(x, metadata, bboxes=meta["boxes"]) returns one row of scores per box."""
 
     def __init__(self, cfg):
         super().__init__()
         assert cfg.DATA.TRAIN_CROP_SIZE == cfg.DATA.TEST_CROP_SIZE
         self.cfg = cfg
         mv = cfg.MVIT
-        if cfg.DETECTION.ENABLE:
-            raise NotImplementedError("DETECTION.ENABLE (ResNetRoIHead) is outside the hot path")
+        self.enable_detection = bool(cfg.DETECTION.ENABLE)
         pool_first = mv.POOL_FIRST
         spatial_size, temporal_size = cfg.DATA.TRAIN_CROP_SIZE, cfg.DATA.NUM_FRAMES
         in_chans = cfg.DATA.INPUT_CHANNEL_NUM[0]
@@ -325,8 +369,21 @@ class MViT(nn.Module):
             i_num_frames //= tstride
         embed_dim = dim_out
         self.norm = norm_layer(embed_dim)
-        self.head = TransformerBasicHead(embed_dim, num_classes, dropout_rate=cfg.MODEL.DROPOUT_RATE,
-                                         act_func=cfg.MODEL.HEAD_ACT)
+        if self.enable_detection:
+            if i_num_frames != temporal_size // self.patch_stride[0]:
+                # the head's temporal pool is sized from the stem (:982): with a temporal Q stride the reference would stop
+                # at head_helper.py's `assert out.shape[2] == 1` in the first forward
+                raise ValueError("DETECTION.ENABLE: MVIT.POOL_Q_STRIDE pools time (%d frames reach the head, its temporal "
+                                 "pool takes %d)" % (i_num_frames, temporal_size // self.patch_stride[0]))
+            self.head = ResNetRoIHead(dim_in=[embed_dim], num_classes=num_classes,
+                                      pool_size=[[temporal_size // self.patch_stride[0], 1, 1]],
+                                      resolution=[[cfg.DETECTION.ROI_XFORM_RESOLUTION] * 2],
+                                      scale_factor=[cfg.DETECTION.SPATIAL_SCALE_FACTOR],
+                                      dropout_rate=cfg.MODEL.DROPOUT_RATE, act_func=cfg.MODEL.HEAD_ACT,
+                                      aligned=cfg.DETECTION.ALIGNED)
+        else:
+            self.head = TransformerBasicHead(embed_dim, num_classes, dropout_rate=cfg.MODEL.DROPOUT_RATE,
+                                             act_func=cfg.MODEL.HEAD_ACT)
         if self.sep_pos_embed:
             trunc_normal_(self.pos_embed_spatial, std=0.02)
             trunc_normal_(self.pos_embed_temporal, std=0.02)
@@ -388,6 +445,10 @@ class MViT(nn.Module):
                 x_orvit, _ = blk_orvit(x_prev, metadata, thw_prev)
                 x = x + x_orvit
         x = ops.layer_norm(x.contiguous(), self.norm.weight, self.norm.bias, self.norm.eps)
+        if self.enable_detection:                                            # :1085-1092, the cls row dropped by addressing
+            if bboxes is None:
+                raise ValueError("DETECTION.ENABLE: MViT.forward needs bboxes=meta['boxes']")
+            return self.head([x], bboxes, thw=thw, cls=1 if self.cls_embed_on else 0)
         x = x[:, 0] if self.cls_embed_on else x.mean(1)
         assert x.device == dev
         return self.head(x.contiguous())

@@ -19,8 +19,12 @@ def train_step(model, optimizer, loss_fun, inputs, labels, meta, cfg, check_nan=
     NaN guard then go into its device tables by one launch right after the loss; the host NaN check is not made whatever
     `check_nan` says, and a NaN surfaces at the next stats.read().  Labels may be the dense rows of mixup.  Under
     cfg.DATA.MULTI_LABEL the labels are multi-hot rows, which have no top-k: the loss and the NaN guard alone are kept
-    (train_net.py:234-238), the top-k columns stay zero."""
-    preds = model(inputs, meta)                                   # train_net.py:86
+    (train_net.py:234-238), the top-k columns stay zero.  Under cfg.DETECTION.ENABLE the model also takes meta["boxes"]
+    ([K,5]: batch index, x1, y1, x2, y2) and returns one row per box; the reference computes no top-k there either (:151)."""
+    if cfg.DETECTION.ENABLE:
+        preds = model(inputs, meta, bboxes=meta["boxes"])         # train_net.py:83-84
+    else:
+        preds = model(inputs, meta)                               # train_net.py:86
     extra_preds = None
     if isinstance(preds, tuple):                                  # :87-88 (EK: (verb, {'verb','noun'}))
         preds, extra_preds = preds
@@ -32,7 +36,7 @@ def train_step(model, optimizer, loss_fun, inputs, labels, meta, cfg, check_nan=
     if stats is not None:
         if cfg.TRAIN.DATASET == "epickitchens":
             stats.update(extra_preds, labels, loss, (loss_dict["verb_loss"], loss_dict["noun_loss"]))
-        elif cfg.DATA.MULTI_LABEL:
+        elif cfg.DATA.MULTI_LABEL or cfg.DETECTION.ENABLE:
             stats.update(None, None, loss, batch=preds.shape[0])
         else:
             stats.update(preds, labels, loss)
@@ -286,10 +290,18 @@ def eval_epoch(val_loader, model, cfg, stats=None):
     Under cfg.DATA.MULTI_LABEL (:433-435, :475 and meters.py:743-747) the predictions and the multi-hot labels of every batch
     are copied into a meters.MultiLabelStats (`stats`, or one made here with room for len(val_loader.dataset) rows, else for
     batches x the first batch's rows) and its read -- {'map', 'samples'} -- is returned: one gather and one
-    focus_average_precision call per epoch."""
+    focus_average_precision call per epoch.
+    Under cfg.DETECTION.ENABLE (:336-366) `stats` is the caller's AVA-style meter: every batch's scores, meta["ori_boxes"] and
+    meta["metadata"] go to its update_stats(preds, ori_boxes, metadata) on the host; the meter is returned."""
     from .slowfast.utils import meters
     model.eval()
     dev = next(model.parameters()).device
+    if cfg.DETECTION.ENABLE:
+        if stats is None:
+            raise ValueError("eval_epoch under DETECTION.ENABLE needs the meter (update_stats(preds, ori_boxes, metadata)) as `stats`")
+        for inputs, _, _, meta in val_loader:
+            _detection_update(model, inputs, meta, stats, dev)
+        return stats
     if cfg.DATA.MULTI_LABEL:
         for inputs, labels, _, meta in val_loader:
             inputs = [x.to(dev) for x in inputs] if isinstance(inputs, (list, tuple)) else inputs.to(dev)
@@ -326,6 +338,22 @@ def eval_epoch(val_loader, model, cfg, stats=None):
     return stats.epoch_stats()
 
 
+def _detection_update(model, inputs, meta, meter, dev):
+    """One batch of the detection branch of the test and validation loops (test_net.py:55-77, train_net.py:336-366): scores of
+    the boxes of meta["boxes"], copied to the host with meta["ori_boxes"] and meta["metadata"] for the meter.  The boxes go to
+    the model as the loader made them, so that a batch index out of range is refused on the host."""
+    if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+        raise NotImplementedError("the multi-rank gather of the detection loops needs all_gather_unaligned, which is not "
+                                  "part of this path")
+    inputs = [x.to(dev) for x in inputs] if isinstance(inputs, (list, tuple)) else inputs.to(dev)
+    boxes = meta["boxes"]
+    meta = {k: (v.to(dev) if isinstance(v, torch.Tensor) else v) for k, v in meta.items()}
+    preds = model(inputs, meta, bboxes=boxes)
+    if isinstance(preds, tuple):
+        preds = preds[0]
+    meter.update_stats(preds.detach().cpu(), meta["ori_boxes"].detach().cpu(), meta["metadata"].detach().cpu())
+
+
 def _takes_metadata(meter):
     import inspect
     try:
@@ -340,10 +368,16 @@ def perform_test(test_loader, model, test_meter, cfg):
     model in eval mode (softmax scores), the meter sums the views per video.  `test_loader` yields
     (inputs, labels, video_idx, meta) like the reference's loaders.  Dict labels, or a meter whose update_stats takes
     `metadata` (meters.EPICTestMeter), take the epickitchens branch (:85-111): both heads and the narration ids go to the
-    meter.  A meters.DeviceTestMeter receives device tensors as they are, without a copy to the host."""
+    meter.  A meters.DeviceTestMeter receives device tensors as they are, without a copy to the host.
+    Under cfg.DETECTION.ENABLE (:55-77) the model takes meta["boxes"] and the meter -- the caller's: AVAMeter is not provided --
+    receives update_stats(preds, ori_boxes, metadata) on the host; finalize_metrics() is called if the meter has one."""
     from .slowfast.utils import meters
     model.eval()
     dev = next(model.parameters()).device
+    if cfg is not None and cfg.DETECTION.ENABLE:
+        for inputs, _, _, meta in test_loader:
+            _detection_update(model, inputs, meta, test_meter, dev)
+        return test_meter.finalize_metrics() if hasattr(test_meter, "finalize_metrics") else None
     ek_meter = _takes_metadata(test_meter)
     on_device = isinstance(test_meter, (meters.DeviceTestMeter, meters.EPICTestMeter))
     for inputs, labels, video_idx, meta in test_loader:

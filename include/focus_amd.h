@@ -286,6 +286,40 @@ int focus_cell_amax_bwd(const void* dy, const int32_t* arg, void* dx, int K, int
                         void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * RoI head pooling (head_helper.py:103-118: AvgPool3d([T,1,1]) -> ROIAlign(resolution, 1/scale_factor, sampling_ratio=0,
+ * aligned) -> MaxPool2d(resolution)) over the token stream, without the [B,C,T,H,W] transpose and without the
+ * [K, PH*PW, C] RoIAlign output:
+ *     pooled[k, c] = max over bins (ph, pw) of RoIAlign(mean_t x[b_k, t, :, :, c])
+ *   x       patch tokens [B, T*H*W, C] read in place: pointer to the first patch token of sample 0, sample b at
+ *           x + b*batch_stride elements (the stream [B, cls + T*H*W, C]: pointer to token `cls`, batch_stride =
+ *           (cls + T*H*W)*C); `dtype`;
+ *   rois    [K,5] fp32 (batch index, x1, y1, x2, y2), the box in input pixels -- the reference's meta["boxes"].  Boxes come
+ *           in any order of batch index.  A batch index that is not an integer in [0, B) is the caller's error (the Python
+ *           side refuses it on the host); the kernels read and write nothing for such a box: pooled = 0, arg = 0, no gradient;
+ *   pooled  [K,C] `dtype`; arg [K,C] int32 = ph*PW + pw of the winning bin, the lowest index among equal bins;
+ *   ws      fp32 [B, H*W, C] (focus_roi_head_workspace_bytes, 16-byte aligned): the temporal mean, summed over t in order.
+ * RoIAlign is torchvision's: the -0.5 shift and no clamp of the box size to 1 when `aligned`, sampling_ratio <= 0 = adaptive
+ * grid ceil(roi / bins), count = max(grid_h*grid_w, 1), samples outside [-1,H] x [-1,W] contribute 0, edges clamped; grid
+ * sizes and neighbour indices are those of focus_roi_align_indices.  Accumulation is fp32.  A box that samples nothing (all
+ * outside, or an empty grid) gives pooled = 0, arg = 0.
+ * backward: dx addressed like x; every patch-token row of every sample is written (samples without boxes: zeros), rows
+ *   between the samples (the cls row) are not touched.  d(k,c) flows through the bilinear weights of bin arg[k,c], divided by
+ *   count and by T, the same for every t.  No atomics: one workgroup owns an (image, channel chunk) slab and adds the boxes
+ *   in index order, so two runs on the same inputs are bit-equal.
+ * Status: K == 0 is FOCUS_OK (forward: nothing written; backward: dx = 0).  FOCUS_ERR_DTYPE unless fp32 / bf16;
+ *   FOCUS_ERR_ALIGN unless C % 4 == 0, batch_stride % 4 == 0 and x / dx aligned to 4 elements; FOCUS_ERR_SHAPE for
+ *   T > 1024, PH*PW > 1024, H*W > 512 (the backward slab lives in LDS), K or B > 65535, batch_stride < T*H*W*C or any
+ *   non-positive size; FOCUS_ERR_WORKSPACE for a short or misaligned ws.
+ * ----------------------------------------------------------------------------------------------*/
+size_t focus_roi_head_workspace_bytes(int B, int H, int W, int C);
+int focus_roi_head_fwd(const void* x, int64_t batch_stride, const float* rois, void* pooled, int32_t* arg, void* ws,
+                       size_t ws_bytes, int B, int T, int H, int W, int C, int K, int PH, int PW, float spatial_scale,
+                       int sampling_ratio, int aligned, int dtype, void* stream);
+int focus_roi_head_bwd(const void* dpooled, const int32_t* arg, const float* rois, void* dx, int64_t batch_stride, int B,
+                       int T, int H, int W, int C, int K, int PH, int PW, float spatial_scale, int sampling_ratio,
+                       int aligned, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * ORViT token plumbing (ORViT/orvit.py:145-147, :152-157, :165-169), one pass each way instead of cat / slice / add chains.
  * x   [B, 1+T*HW, C]     residual stream (cls row + patch tokens)
  * obj [B, T, O, C]       object tokens
