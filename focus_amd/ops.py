@@ -3708,3 +3708,87 @@ def average_precision(scores, labels):
                                              labels.stride(0) if N > 1 else C, N, C, _p(npos), _p(ap), _p(summary), _p(flag),
                                              _p(ws), nbytes, _stream()), "average_precision")
     return ap, npos, summary, flag
+
+
+# --------------------------------------------------------------------------------------------------
+# the AVA evaluation (csrc/ava_eval.hip)
+# --------------------------------------------------------------------------------------------------
+AVA_GT_OVERFLOW, AVA_BAD_INDEX = 1, 2                                      # the bits of focus_ava_match's flag
+VOC_BAD_SCORE, VOC_TP_ABOVE_GT, VOC_GT_ABOVE_TOTAL = 1, 2, 4               # the bits of focus_voc_ap's flag
+AVA_GT_CAP = 64                                                            # ground-truth rows per (image, class)
+
+
+def _need_table(t, dtype, shape, what, fn):
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError("focus_amd: %s takes a contiguous %s %s %s; got %s %s" % (
+            fn, str(dtype).replace("torch.", ""), what, list(shape), t.dtype, tuple(t.shape)))
+
+
+def ava_match(boxes, num_classes, grp_off, det_rows, grp_image, gt_off, gt_class, gt_boxes, whitelist, out=None, counts=None,
+              flag=None):
+    """The greedy match of the AVA evaluation per (image, class) (include/focus_amd.h): boxes float32 [K,4] (x1, y1, x2, y2) in
+    arrival order; grp_off int64 [G+1], det_rows int64 [K], grp_image int64 [G] group the rows by image; gt_off int64 [I+1],
+    gt_class int32 [R], gt_boxes float64 [R,4] are the ground truth by image; whitelist uint8 [C].  Returns (bytes uint8 [K,C]:
+    0 not evaluated, 1 false positive, 2 true positive; counts int64 [2,C]: judged rows and true positives per class, added
+    to; flag int32 [1]: AVA_GT_OVERFLOW | AVA_BAD_INDEX, sticky).  One launch, no sync, no CPU fallback."""
+    _need_gpu(boxes, grp_off, det_rows, grp_image, gt_off, gt_class, gt_boxes, whitelist, out, counts, flag)
+    fn = "ava_match"
+    C = int(num_classes)
+    if boxes.dim() != 2 or boxes.shape[1] != 4 or C < 1:
+        raise ValueError("focus_amd: ava_match takes boxes [K,4] and num_classes >= 1; got %s, %d" % (tuple(boxes.shape), C))
+    K, G, I, R = boxes.shape[0], grp_image.shape[0], gt_off.shape[0] - 1, gt_class.shape[0]
+    dev = boxes.device
+    _need_table(boxes, torch.float32, (K, 4), "boxes", fn)
+    _need_table(grp_off, torch.int64, (G + 1,), "grp_off", fn)
+    _need_table(det_rows, torch.int64, (K,), "det_rows", fn)
+    _need_table(grp_image, torch.int64, (G,), "grp_image", fn)
+    _need_table(gt_off, torch.int64, (I + 1,), "gt_off", fn)
+    _need_table(gt_class, torch.int32, (R,), "gt_class", fn)
+    _need_table(gt_boxes, torch.float64, (R, 4), "gt_boxes", fn)
+    _need_table(whitelist, torch.uint8, (C,), "whitelist", fn)
+    if out is None:
+        out = torch.zeros((K, C), dtype=torch.uint8, device=dev)
+    if counts is None:
+        counts = torch.zeros((2, C), dtype=torch.int64, device=dev)
+    if flag is None:
+        flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    _need_table(out, torch.uint8, (K, C), "out", fn)
+    _need_table(counts, torch.int64, (2, C), "counts", fn)
+    _need_table(flag, torch.int32, (1,), "flag", fn)
+    if any(t.device != dev for t in (grp_off, det_rows, grp_image, gt_off, gt_class, gt_boxes, whitelist, out, counts, flag)):
+        raise ValueError("focus_amd: ava_match takes all its tables on one device")
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().focus_ava_match(_p(boxes), K, C, _p(grp_off), _p(det_rows), _p(grp_image), G, _p(gt_off),
+                                              _p(gt_class), _p(gt_boxes), I, _p(whitelist), _p(out), C, _p(counts), _p(flag),
+                                              _stream()), fn)
+    return out, counts, flag
+
+
+def voc_average_precision(scores, bytes_, n_gt, total_gt):
+    """The VOC average precision per class from ava_match's byte table (include/focus_amd.h): scores float32 or bfloat16 [N,C]
+    (a row stride is passed as it is), bytes_ uint8 [N,C], n_gt int64 [C] the ground-truth rows per class, total_gt a host
+    integer >= their sum.  Equal scores are ordered by descending row index.  Returns (ap float64 [C], NaN without ground
+    truth; summary float64 [2] = (mean over the classes with ground truth, their number); flag int32 [1]: VOC_BAD_SCORE |
+    VOC_TP_ABOVE_GT | VOC_GT_ABOVE_TOTAL).  Nothing is synchronised and nothing is read back here; no CPU fallback."""
+    _need_gpu(scores, bytes_, n_gt)
+    if scores.dim() != 2 or scores.dtype not in (torch.float32, torch.bfloat16) or scores.shape[1] < 1 or \
+            (scores.shape[0] > 0 and scores.stride(1) != 1):
+        raise ValueError("focus_amd: voc_average_precision takes float32 or bfloat16 scores [N,C], C >= 1, with unit column "
+                         "stride; got %s %s with strides %s" % (scores.dtype, tuple(scores.shape), tuple(scores.stride())))
+    N, C = scores.shape
+    dev = scores.device
+    _need_table(bytes_, torch.uint8, (N, C), "bytes", "voc_average_precision")
+    _need_table(n_gt, torch.int64, (C,), "n_gt", "voc_average_precision")
+    total_gt = int(total_gt)
+    if total_gt < 0 or bytes_.device != dev or n_gt.device != dev:
+        raise ValueError("focus_amd: voc_average_precision takes total_gt >= 0 and all its tables on one device")
+    ap = torch.zeros(C, dtype=torch.float64, device=dev)
+    summary = torch.zeros(2, dtype=torch.float64, device=dev)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    nbytes = L.focus_voc_ap_workspace_bytes(N, C, total_gt)
+    ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.focus_voc_ap(_p(scores), _dt(scores), scores.stride(0) if N > 1 else C, _p(bytes_), C, N, C, _p(n_gt),
+                                  total_gt, _p(ap), _p(summary), _p(flag), _p(ws), nbytes, _stream()), "voc_ap")
+    return ap, summary, flag

@@ -149,6 +149,10 @@ def _defaults():
                           POOL_KV_STRIDE_ADAPTIVE=None, POOL_Q_STRIDE=[], POOL_KVQ_KERNEL=None, ZERO_DECAY_POS_CLS=True,
                           NORM_STEM=False, SEP_POS_EMBED=False, DROPOUT_RATE=0.0, POOL_KV_IGNORE_111_KERNEL=False))
     C.DETECTION = CfgNode(dict(ENABLE=False, ALIGNED=True, SPATIAL_SCALE_FACTOR=16, ROI_XFORM_RESOLUTION=7))
+    # what AVAMeter and ava_helper.load_image_lists read (defaults.py:917-974 of the reference; its directories name one machine)
+    C.AVA = CfgNode(dict(FRAME_DIR="", FRAME_LIST_DIR="", ANNOTATION_DIR="", TRAIN_LISTS=["train.csv"], TEST_LISTS=["val.csv"],
+                         FULL_TEST_ON_VAL=False, LABEL_MAP_FILE="ava_action_list_v2.2_for_activitynet_2019.pbtxt",
+                         EXCLUSION_FILE="ava_val_excluded_timestamps_v2.2.csv", GROUNDTRUTH_FILE="ava_val_v2.2.csv"))
     C.DATA_LOADER = CfgNode(dict(NUM_WORKERS=8, PIN_MEMORY=True, ENABLE_MULTI_THREAD_DECODE=False))
     C.TENSORBOARD = CfgNode(dict(ENABLE=True))
     C.NUM_GPUS = 1

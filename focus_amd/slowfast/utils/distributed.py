@@ -46,6 +46,43 @@ def all_reduce(tensors, average=True):
     return [flat[i].to(t.dtype) for i, t in enumerate(tensors)]
 
 
+_GLOO_GROUP = None
+
+
+def _global_gloo_group():
+    """All ranks over gloo: the world itself when it is a gloo world, else a side group made once."""
+    global _GLOO_GROUP
+    if dist.get_backend() == "gloo":
+        return dist.group.WORLD
+    if _GLOO_GROUP is None:
+        _GLOO_GROUP = dist.new_group(backend="gloo")
+    return _GLOO_GROUP
+
+
+def all_gather_unaligned(data, group=None):
+    """distributed.py:229-265: all-gather of any picklable object, one per rank and of any size -> the list of the ranks'
+    objects in rank order.  The pickles travel as byte tensors over a gloo group (on the host), padded to the longest; the
+    lengths are gathered first."""
+    import pickle
+    if get_world_size() == 1:
+        return [data]
+    if group is None:
+        group = _global_gloo_group()
+    world = dist.get_world_size(group)
+    if world == 1:
+        return [data]
+    device = torch.device("cpu" if dist.get_backend(group) == "gloo" else "cuda")
+    payload = torch.frombuffer(bytearray(pickle.dumps(data)), dtype=torch.uint8).to(device)
+    sizes = [torch.zeros(1, dtype=torch.int64, device=device) for _ in range(world)]
+    dist.all_gather(sizes, torch.tensor([payload.numel()], dtype=torch.int64, device=device), group=group)
+    sizes = [int(s.item()) for s in sizes]
+    padded = torch.zeros(max(sizes), dtype=torch.uint8, device=device)
+    padded[:payload.numel()] = payload
+    parts = [torch.empty_like(padded) for _ in sizes]
+    dist.all_gather(parts, padded, group=group)
+    return [pickle.loads(p.cpu().numpy().tobytes()[:n]) for n, p in zip(sizes, parts)]
+
+
 def init_distributed_training(cfg):
     """distributed.py:268-285: one process group per machine (the ranks that share xGMI)."""
     global _LOCAL_PROCESS_GROUP

@@ -343,6 +343,242 @@ class MultiLabelStats(object):
         return out
 
 
+def get_ava_mini_groundtruth(full_groundtruth):
+    """meters.py:32-47: the ground truth of the key frames whose second is a multiple of 4, the subset the validation
+    epochs are scored on unless AVA.FULL_TEST_ON_VAL."""
+    from collections import defaultdict
+    ret = [defaultdict(list), defaultdict(list), defaultdict(list)]
+    for i in range(3):
+        for key in full_groundtruth[i].keys():
+            if int(key.split(",")[1]) % 4 == 0:
+                ret[i][key] = full_groundtruth[i][key]
+    return ret
+
+
+class AVAMeter(object):
+    """meters.py:50-232 without the timers and the JSON logger: the rows of an epoch are kept on the host and scored by
+    ava_eval_helper.evaluate_ava at the end.  `mode` is 'train', 'val' or 'test'; 'test', and 'val' under
+    AVA.FULL_TEST_ON_VAL, are scored on the whole ground truth, 'val' otherwise on the mini ground truth.  The reference
+    writes detections_latest.csv and groundtruth_latest.csv on every evaluation; here only with write_csv=True."""
+
+    def __init__(self, overall_iters, cfg, mode):
+        import os
+        from collections import deque
+        from . import ava_eval_helper
+        from ..datasets import ava_helper
+        if mode not in ("train", "val", "test"):
+            raise NotImplementedError("Unknown mode: {}".format(mode))
+        self.cfg = cfg
+        self.lr = None
+        self.loss = deque(maxlen=int(cfg.LOG_PERIOD))
+        self.full_ava_test = cfg.AVA.FULL_TEST_ON_VAL
+        self.mode = mode
+        self.overall_iters = overall_iters
+        self.full_map = None
+        self.excluded_keys = ava_eval_helper.read_exclusions(os.path.join(cfg.AVA.ANNOTATION_DIR, cfg.AVA.EXCLUSION_FILE))
+        self.categories, self.class_whitelist = ava_eval_helper.read_labelmap(
+            os.path.join(cfg.AVA.ANNOTATION_DIR, cfg.AVA.LABEL_MAP_FILE))
+        self.full_groundtruth = ava_eval_helper.read_csv(os.path.join(cfg.AVA.ANNOTATION_DIR, cfg.AVA.GROUNDTRUTH_FILE),
+                                                         self.class_whitelist)
+        self.mini_groundtruth = get_ava_mini_groundtruth(self.full_groundtruth)
+        _, self.video_idx_to_name = ava_helper.load_image_lists(cfg, mode == "train")
+        self.output_dir = cfg.OUTPUT_DIR
+        self.reset()
+
+    def _groundtruth(self):
+        full = self.mode == "test" or (self.full_ava_test and self.mode == "val")
+        return self.full_groundtruth if full else self.mini_groundtruth
+
+    def reset(self):
+        self.loss.clear()
+        self.all_preds, self.all_ori_boxes, self.all_metadata = [], [], []
+
+    def update_stats(self, preds, ori_boxes, metadata, loss=None, lr=None):
+        """preds [n,C] scores, ori_boxes [n,5] (batch index, x1, y1, x2, y2), metadata [n,2] (video index, second); kept in
+        'val' and 'test' mode only, as in the reference."""
+        if self.mode in ["val", "test"]:
+            self.all_preds.append(preds)
+            self.all_ori_boxes.append(ori_boxes)
+            self.all_metadata.append(metadata)
+        if loss is not None:
+            self.loss.append(float(loss))
+        if lr is not None:
+            self.lr = lr
+
+    def _rows(self):
+        if not self.all_preds:
+            raise RuntimeError("AVAMeter.finalize_metrics: no rows were received (mode %r keeps %s)" % (
+                self.mode, "rows" if self.mode in ("val", "test") else "none"))
+        return torch.cat(self.all_preds, dim=0), torch.cat(self.all_ori_boxes, dim=0), torch.cat(self.all_metadata, dim=0)
+
+    def finalize_metrics(self, log=True, write_csv=False):
+        """-> self.full_map, the mAP@0.5IOU over the rows received since the last reset."""
+        from . import ava_eval_helper
+        preds, ori_boxes, metadata = self._rows()
+        self.full_map = ava_eval_helper.evaluate_ava(preds, ori_boxes, metadata, self.excluded_keys, self.class_whitelist,
+                                                     self.categories, groundtruth=self._groundtruth(),
+                                                     video_idx_to_name=self.video_idx_to_name, write_csv=write_csv)
+        if log:
+            _ava_log({"mode": self.mode, "map": self.full_map})
+        return self.full_map
+
+    def log_epoch_stats(self, cur_epoch):
+        """The epoch's record ({'_type', 'cur_epoch', 'mode', 'map'}) in 'val' and 'test' mode; None in 'train' mode."""
+        if self.mode not in ["val", "test"]:
+            return None
+        self.finalize_metrics(log=False)
+        stats = {"_type": "{}_epoch".format(self.mode), "cur_epoch": "{}".format(cur_epoch + 1), "mode": self.mode,
+                 "map": self.full_map}
+        _ava_log(stats)
+        return stats
+
+
+def _ava_log(stats):
+    import logging
+    logging.getLogger(__name__).info("json_stats: %s", stats)
+
+
+class DeviceAVAMeter(AVAMeter):
+    """AVAMeter with the evaluation on the device (csrc/ava_eval.hip).  At construction the ground truth in use is uploaded
+    once: a dense (video index, second) -> image lookup (-1 no ground truth, -2 excluded), the ground-truth rows by image
+    (class ids, float64 boxes) and the rows per class.  `update_stats` keeps the device tensors it is given and does not
+    synchronise.  `finalize_metrics` groups the rows by image with one stable sort, runs focus_ava_match and focus_voc_ap,
+    makes one small copy to the host -- its only sync -- and raises for a set flag.  `self.ap` is the per-class table
+    (float64 [C] on the device, NaN without ground truth).  Equal scores within a class are ordered by descending row of
+    the concatenated update_stats calls, like the host meter.  With several ranks every rank's rows are gathered once, in
+    finalize_metrics (a length gather and one padded all_gather), rank after rank."""
+
+    def __init__(self, overall_iters, cfg, mode, device="cuda"):
+        super().__init__(overall_iters, cfg, mode)
+        import numpy as np
+        self.device = torch.device(device)
+        self.ap = None
+        gt = self._groundtruth()
+        keys = [k for k in gt[0] if k not in self.excluded_keys]
+        ids = [c["id"] for c in self.categories]
+        if not ids or min(ids) < 1:
+            raise ValueError("Classes should be 1-indexed.")
+        self.num_classes = max(ids)
+        gt_off, gt_class, gt_boxes = [0], [], []
+        for k in keys:
+            for b, l in zip(gt[0][k], gt[1][k]):
+                gt_class.append(int(l))
+                gt_boxes.append([b[1], b[0], b[3], b[2]])       # the reader's [y1, x1, y2, x2] -> (x1, y1, x2, y2)
+            gt_off.append(len(gt_class))
+        gt_class = np.asarray(gt_class, dtype=np.int32).reshape(-1)
+        if gt_class.size and (gt_class.min() < 1 or gt_class.max() > self.num_classes):
+            raise ValueError("DeviceAVAMeter: a ground-truth class id lies outside 1..%d" % self.num_classes)
+        n_gt = np.bincount(gt_class - 1, minlength=self.num_classes).astype(np.int64)
+        self.total_gt = int(n_gt.sum())
+        video_of = {name: i for i, name in enumerate(self.video_idx_to_name)}
+        split = lambda k: (k.rsplit(",", 1)[0], int(k.rsplit(",", 1)[1]))
+        secs = [split(k)[1] for k in list(keys) + list(self.excluded_keys) if split(k)[0] in video_of]
+        self._secs = max(secs) + 1 if secs else 1
+        lookup = np.full((max(len(video_of), 1), self._secs), -1, dtype=np.int64)
+        for i, k in enumerate(keys):
+            name, sec = split(k)
+            if name in video_of and sec >= 0:
+                lookup[video_of[name], sec] = i
+        for k in self.excluded_keys:
+            name, sec = split(k)
+            if name in video_of and sec >= 0:
+                lookup[video_of[name], sec] = -2
+        dev = self.device
+        self._lookup = torch.from_numpy(lookup).to(dev)
+        self._gt_off = torch.tensor(gt_off, dtype=torch.int64, device=dev)
+        self._gt_class = torch.from_numpy(gt_class).to(dev)
+        self._gt_boxes = torch.tensor(gt_boxes, dtype=torch.float64, device=dev).reshape(len(gt_boxes), 4)
+        self._n_gt = torch.from_numpy(n_gt).to(dev)
+
+    def update_stats(self, preds, ori_boxes, metadata, loss=None, lr=None):
+        """Device tensors are kept as they are; host tensors are copied over without blocking.  `loss` is kept as given (a
+        0-d device tensor is not read here)."""
+        if self.mode in ["val", "test"]:
+            self.all_preds.append(preds.detach().to(self.device, non_blocking=True))
+            self.all_ori_boxes.append(ori_boxes.detach().to(self.device, non_blocking=True))
+            self.all_metadata.append(metadata.detach().to(self.device, non_blocking=True))
+        if loss is not None:
+            self.loss.append(loss)
+        if lr is not None:
+            self.lr = lr
+
+    def _gathered(self):
+        preds, ori_boxes, metadata = self._rows()
+        world = _distributed_world()
+        if world == 1:
+            return preds, ori_boxes, metadata
+        import torch.distributed as dist
+        C = preds.shape[1]
+        both = torch.cat([preds.double(), ori_boxes.double().reshape(-1, 5), metadata.double().reshape(preds.shape[0], -1)[:, :2]],
+                         dim=1)                                                # fp32 and bf16 values are exact in double
+        counts = [torch.zeros(1, dtype=torch.int64, device=self.device) for _ in range(world)]
+        dist.all_gather(counts, torch.tensor([both.shape[0]], dtype=torch.int64, device=self.device))
+        counts = [int(c) for c in torch.cat(counts).cpu()]
+        padded = torch.zeros((max(counts), both.shape[1]), dtype=torch.float64, device=self.device)
+        padded[:both.shape[0]] = both
+        parts = [torch.empty_like(padded) for _ in range(world)]
+        dist.all_gather(parts, padded)                                        # the one gather of the epoch
+        both = torch.cat([p[:c] for p, c in zip(parts, counts)])
+        return both[:, :C].to(preds.dtype), both[:, C:C + 5].float(), both[:, C + 5:]
+
+    def finalize_metrics(self, log=True, write_csv=False):
+        from focus_amd import ops
+        if write_csv:
+            raise NotImplementedError("DeviceAVAMeter writes no CSV files: score the epoch with AVAMeter(write_csv=True)")
+        preds, ori_boxes, metadata = self._gathered()
+        K, C = preds.shape
+        if C < self.num_classes:
+            raise ValueError("DeviceAVAMeter: %d score columns for class ids up to %d" % (C, self.num_classes))
+        if preds.dtype not in (torch.float32, torch.bfloat16):
+            preds = preds.float()
+        preds = preds.contiguous()
+        dev = self.device
+        boxes = ori_boxes.reshape(K, 5)[:, 1:5].float().contiguous()
+        metadata = metadata.reshape(K, -1).double()
+        vid, sec = torch.round(metadata[:, 0]).long(), torch.round(metadata[:, 1]).long()
+        V, S = self._lookup.shape
+        inside = (vid >= 0) & (vid < V) & (sec >= 0) & (sec < S)
+        image = torch.where(inside, self._lookup[vid.clamp(0, V - 1), sec.clamp(0, S - 1)], torch.full_like(vid, -1))
+        # 1. group by image: one stable sort of the rows by (video, second); the rows of excluded images go to the end and
+        #    belong to no group.  The number of groups stays on the device: K groups are passed, the surplus is empty.
+        last = torch.iinfo(torch.int64).max
+        key = torch.where(image == -2, torch.full_like(vid, last), vid * (1 << 32) + (sec & 0xFFFFFFFF))
+        skey, det_rows = torch.sort(key, stable=True)
+        first = torch.ones(K, dtype=torch.bool, device=dev)
+        first[1:] = skey[1:] != skey[:-1]
+        gid = torch.cumsum(first.long(), 0) - 1
+        slot = torch.where(first, gid, torch.full_like(gid, K + 1))           # rows that open no group write to a spare slot
+        end = (image != -2).sum().reshape(1)                                  # where the excluded rows begin
+        grp_off = end.expand(K + 2).clone()                                   # the group they open there is empty, like the surplus
+        grp_off.scatter_(0, slot, torch.arange(K, device=dev))
+        grp_off = grp_off[:K + 1].contiguous()
+        grp_image = torch.full((K + 2,), -1, dtype=torch.int64, device=dev)
+        grp_image.scatter_(0, slot, image[det_rows])
+        whitelist = torch.zeros(C, dtype=torch.uint8, device=dev)
+        ids = [c - 1 for c in self.class_whitelist if 1 <= c <= self.num_classes]
+        whitelist[torch.tensor(ids, dtype=torch.int64, device=dev)] = 1
+        n_gt = torch.zeros(C, dtype=torch.int64, device=dev)
+        n_gt[:self.num_classes] = self._n_gt
+        # 2. the match, 3. the average precision
+        self.bytes, self.counts, mflag = ops.ava_match(boxes, C, grp_off, det_rows.contiguous(), grp_image[:K].contiguous(),
+                                                       self._gt_off, self._gt_class, self._gt_boxes, whitelist)
+        self.ap, summary, vflag = ops.voc_average_precision(preds, self.bytes, n_gt, self.total_gt)
+        t = torch.cat([summary, mflag.double(), vflag.double()]).cpu()        # 4. the one copy to the host
+        mflag, vflag = int(t[2]), int(t[3])                                   # 5. the flags
+        if mflag & ops.AVA_GT_OVERFLOW:
+            raise RuntimeError("DeviceAVAMeter: an image has more than %d ground-truth rows of one class" % ops.AVA_GT_CAP)
+        if mflag & ops.AVA_BAD_INDEX:
+            raise RuntimeError("DeviceAVAMeter: the group tables are inconsistent")
+        if vflag & ops.VOC_BAD_SCORE:
+            raise ValueError("DeviceAVAMeter: a detection score is not finite")
+        if vflag & (ops.VOC_TP_ABOVE_GT | ops.VOC_GT_ABOVE_TOTAL):
+            raise ValueError("Number of true positives must be smaller than num_gt.")
+        self.full_map = float(t[0])
+        if log:
+            _ava_log({"mode": self.mode, "map": self.full_map})
+        return self.full_map
+
+
 class EPICTestMeter(object):
     """meters.py:1134-1273 with the two tables on the device: two focus_view_accumulate launches per batch; the narration ids
     stay on the host, indexed from the host clip_ids."""

@@ -291,8 +291,9 @@ def eval_epoch(val_loader, model, cfg, stats=None):
     are copied into a meters.MultiLabelStats (`stats`, or one made here with room for len(val_loader.dataset) rows, else for
     batches x the first batch's rows) and its read -- {'map', 'samples'} -- is returned: one gather and one
     focus_average_precision call per epoch.
-    Under cfg.DETECTION.ENABLE (:336-366) `stats` is the caller's AVA-style meter: every batch's scores, meta["ori_boxes"] and
-    meta["metadata"] go to its update_stats(preds, ori_boxes, metadata) on the host; the meter is returned."""
+    Under cfg.DETECTION.ENABLE (:336-366) `stats` is the AVA meter (meters.AVAMeter, meters.DeviceAVAMeter, or the caller's):
+    every batch's scores, meta["ori_boxes"] and meta["metadata"] go to its update_stats(preds, ori_boxes, metadata) -- on the
+    host, for a DeviceAVAMeter on the device; the meter is returned, to be read with log_epoch_stats or finalize_metrics."""
     from .slowfast.utils import meters
     model.eval()
     dev = next(model.parameters()).device
@@ -341,17 +342,24 @@ def eval_epoch(val_loader, model, cfg, stats=None):
 def _detection_update(model, inputs, meta, meter, dev):
     """One batch of the detection branch of the test and validation loops (test_net.py:55-77, train_net.py:336-366): scores of
     the boxes of meta["boxes"], copied to the host with meta["ori_boxes"] and meta["metadata"] for the meter.  The boxes go to
-    the model as the loader made them, so that a batch index out of range is refused on the host."""
-    if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
-        raise NotImplementedError("the multi-rank gather of the detection loops needs all_gather_unaligned, which is not "
-                                  "part of this path")
+    the model as the loader made them, so that a batch index out of range is refused on the host.  A meters.DeviceAVAMeter
+    receives the device tensors as they are and gathers the ranks once, when it is read; for any other meter the three tensors
+    of every rank are gathered here with all_gather_unaligned, as the reference does (test_net.py:71-74)."""
+    from .slowfast.utils import distributed as du
+    from .slowfast.utils import meters
     inputs = [x.to(dev) for x in inputs] if isinstance(inputs, (list, tuple)) else inputs.to(dev)
     boxes = meta["boxes"]
     meta = {k: (v.to(dev) if isinstance(v, torch.Tensor) else v) for k, v in meta.items()}
     preds = model(inputs, meta, bboxes=boxes)
     if isinstance(preds, tuple):
         preds = preds[0]
-    meter.update_stats(preds.detach().cpu(), meta["ori_boxes"].detach().cpu(), meta["metadata"].detach().cpu())
+    if isinstance(meter, meters.DeviceAVAMeter):
+        meter.update_stats(preds.detach(), meta["ori_boxes"].detach(), meta["metadata"].detach())
+        return
+    rows = [preds.detach().cpu(), meta["ori_boxes"].detach().cpu(), meta["metadata"].detach().cpu()]
+    if du.get_world_size() > 1:
+        rows = [torch.cat(du.all_gather_unaligned(t), dim=0) for t in rows]
+    meter.update_stats(*rows)
 
 
 def _takes_metadata(meter):
@@ -369,8 +377,9 @@ def perform_test(test_loader, model, test_meter, cfg):
     (inputs, labels, video_idx, meta) like the reference's loaders.  Dict labels, or a meter whose update_stats takes
     `metadata` (meters.EPICTestMeter), take the epickitchens branch (:85-111): both heads and the narration ids go to the
     meter.  A meters.DeviceTestMeter receives device tensors as they are, without a copy to the host.
-    Under cfg.DETECTION.ENABLE (:55-77) the model takes meta["boxes"] and the meter -- the caller's: AVAMeter is not provided --
-    receives update_stats(preds, ori_boxes, metadata) on the host; finalize_metrics() is called if the meter has one."""
+    Under cfg.DETECTION.ENABLE (:55-77) the model takes meta["boxes"] and the meter -- meters.AVAMeter, or any object with
+    that method -- receives update_stats(preds, ori_boxes, metadata) on the host, a meters.DeviceAVAMeter on the device;
+    finalize_metrics() is called if the meter has one (for the two AVA meters it returns the mAP@0.5IOU)."""
     from .slowfast.utils import meters
     model.eval()
     dev = next(model.parameters()).device

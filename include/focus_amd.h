@@ -1094,6 +1094,65 @@ size_t focus_average_precision_workspace_bytes(int N, int C);
 int focus_average_precision(const float* scores, int64_t lds, const float* labels, int64_t ldl, int N, int C, int64_t* npos,
                             double* ap, double* summary, int32_t* flag, void* workspace, size_t workspace_bytes, void* stream);
 
+/* -------------------------------------------------------------------------------------------------
+ * The AVA evaluation (ava_eval.hip; PascalBoxes mAP@0.5IOU of the reference: slowfast/utils/ava_eval_helper.py:174-287,
+ * ava_evaluation/per_image_evaluation.py:261-352, object_detection_evaluation.py:640-830, metrics.py:21-125).  No float
+ * atomics (the counters are integers) and no data-dependent order: the same arguments give the same bits.
+ *
+ * focus_ava_match: the greedy match per (image, class).
+ *   boxes [K,4] fp32 (x1, y1, x2, y2), the detection rows in arrival order.  A row with not (y1 < y2 and x1 < x2) is
+ *   invalid and is not judged.
+ *   Groups: the rows of one image.  grp_off int64 [n_groups + 1] are offsets into det_rows int64 [K], which lists the rows
+ *   of group 0, then of group 1, ..., each group in ascending row (= arrival) order; rows of excluded images are listed
+ *   nowhere, so fewer than K entries may be in use.  grp_image int64 [n_groups]: the ground-truth image of the group,
+ *   or a negative value when the image has no ground truth (all its rows are false positives).
+ *   Ground truth: gt_off int64 [n_images + 1] offsets into gt_class int32 [.] (1-based class ids) and gt_boxes float64 [.,4]
+ *   (x1, y1, x2, y2), the rows of an image in file order.
+ *   whitelist uint8 [C]: class c (0-based; class id c + 1) is evaluated when its byte is non-zero.
+ *   Per (group, whitelisted class) the valid rows are walked in order.  In float64, boxes widened,
+ *       area = (y2 - y1) (x2 - x1)    ih = max(min(y2, y2') - max(y1, y1'), 0)    iw likewise    inter = ih iw
+ *       iou = inter / (area + area' - inter)
+ *   against the ground-truth rows of that class in the image; the FIRST maximum is the candidate; the row is a true positive
+ *   when iou >= 0.5 and the candidate has not been taken, and takes it; otherwise it is a false positive.
+ *   out uint8 [K,C] with row stride ldo: 1 false positive, 2 true positive, written for judged (row, class) pairs only;
+ *   every other byte is left as the caller set it (0: not evaluated).  counts int64 [2,C]: the judged rows and the true
+ *   positives per class are ADDED.  flag int32 [1], sticky (OR-ed): bit 0 an (image, class) has more than 64 ground-truth
+ *   rows, none of its rows is judged; bit 1 an index of the group tables is out of range, the entry is skipped.
+ *   One launch.  Status, in this order: FOCUS_ERR_NULL (out, counts, flag, whitelist; with K > 0 boxes or a group table;
+ *     with n_images > 0 a ground-truth table); FOCUS_ERR_SHAPE (K < 0, C < 1, C > 65535 * 256, n_groups < 0 or >= 2^31,
+ *     n_images < 0, ldo < C); FOCUS_OK without a launch for K == 0 or n_groups == 0.  The scores are not an argument: the
+ *     match does not look at them.
+ *
+ * focus_voc_ap: the VOC average precision per class.  scores [N,C] fp32 or bf16 with row stride lds, bytes uint8 [N,C] with
+ *   row stride ldb as focus_ava_match writes them (0 not evaluated, 2 true positive, anything else false positive), n_gt
+ *   int64 [C] the ground-truth rows per class, total_gt >= sum of n_gt (a host value: it sizes the workspace).
+ *   The evaluated rows of class c are ordered by descending score, equal scores by DESCENDING row index.  With pos_j the
+ *   0-based rank of the j-th true positive in that order (j = 1..m), n = n_gt[c]:
+ *       p_j = j / (pos_j + 1)    env_j = max_{j' >= j} p_j'    AP_c = sum_j (j / n - (j - 1) / n) env_j        (float64)
+ *   The ranks are counted, nothing is sorted.  Order of the sum: with L = ceil(m / 256), part k (k = 0..255) adds the terms
+ *   of j = min(k L + L, m) down to k L + 1, in descending j, starting from 0; the 256 parts are folded by halving (part s +=
+ *   part s + h for h = 128, ..., 1).
+ *   ap [C] float64: NaN for n == 0, 0 without an evaluated row.  summary float64 [2]: the mean of ap over the classes with
+ *   n > 0 (NaN when there is none), added in ascending class order by one thread, and their number.
+ *   flag int32 [1], OVERWRITTEN: bit 0 a score of an evaluated row is not finite; bit 1 more true positives than n in a
+ *   class with n > 0 (the reference's ValueError), its ap is NaN and it is left out of the mean; bit 2 the n_gt add up to more than
+ *   total_gt, the classes without room likewise.
+ *   workspace: focus_voc_ap_workspace_bytes(N, C, total_gt) bytes, 8-byte aligned (it also holds a class-major copy of the
+ *   evaluated scores: 5 bytes per (row, class)); five launches on the caller's stream.
+ *   Status, in this order: FOCUS_ERR_NULL (n_gt, ap, summary, flag, workspace; scores or bytes with N > 0); FOCUS_ERR_SHAPE
+ *     (N < 0, N > 2^31 - 257, ceil(N / 256) C >= 2^31, C < 1, C > 65535, total_gt < 0, a row stride below C); FOCUS_ERR_DTYPE; FOCUS_ERR_ALIGN;
+ *     FOCUS_ERR_WORKSPACE.
+ *     N == 0 is scored like any table: every class with ground truth gets 0.
+ * ----------------------------------------------------------------------------------------------*/
+int focus_ava_match(const float* boxes, int64_t K, int C, const int64_t* grp_off, const int64_t* det_rows,
+                    const int64_t* grp_image, int64_t n_groups, const int64_t* gt_off, const int32_t* gt_class,
+                    const double* gt_boxes, int64_t n_images, const uint8_t* whitelist, uint8_t* out, int64_t ldo,
+                    int64_t* counts, int32_t* flag, void* stream);
+size_t focus_voc_ap_workspace_bytes(int64_t N, int C, int64_t total_gt);
+int focus_voc_ap(const void* scores, int dtype, int64_t lds, const uint8_t* bytes, int64_t ldb, int64_t N, int C,
+                 const int64_t* n_gt, int64_t total_gt, double* ap, double* summary, int32_t* flag, void* workspace,
+                 size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
