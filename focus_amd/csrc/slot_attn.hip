@@ -300,7 +300,9 @@ __device__ __forceinline__ sbf16x8 slot_frag(const bf16_t* base, int slot, int K
 //   * the other operand (v or k rows, channel on the lane, the same row order) is gathered from a wave-private LDS
 //     image of the 32 rows by ds_read_b64_tr_b16; row pitch 2 D + 32 bytes = 8 * odd dwords: the 8 rows one 32-lane
 //     half touches sit on 8 different 8-bank groups, conflict-free;
-//   * 2 * D / 16 MFMAs per 32 rows replace 2560 VALU instructions.  The image is filled by 16-byte row-contiguous loads
+//   * 2 * D / 16 MFMAs per 32 rows replace 2560 VALU instructions (the forward issues each twice, for the bf16 weight and
+//     for its rounding residue: 22.0 -> 22.15 us per launch at B = 32, N = 4096, D = 192, the slot update's step within its
+//     spread).  The image is filled by 16-byte row-contiguous loads
 //     (the 32 rows are one contiguous 64 D-byte run of HBM); no workgroup barrier until the final 4-wave combine, whose
 //     buffer reuses the wave's own image.
 typedef __attribute__((ext_vector_type(4))) short ss16x4;
@@ -399,8 +401,11 @@ __device__ __forceinline__ void slot_store_rows(char* img, su32x4 (&r)[2 * KS], 
     }
 }
 // acc[ct][r] += sum over the 32 rows of a[row][slot 4g + r] * img[row][16 ct + (lane & 15)]
-template <int KS>
-__device__ __forceinline__ void slot_rank_mfma(sf32x4 (&acc)[2 * KS], const char* img, sbf16x8 a, int lane) {
+// SPLIT: a_lo holds what the bf16 rounding of a took away (a = bf16(x), a_lo = bf16(x - a)); both halves meet the same
+// image fragment, so the sum carries x to 16 bits and the caller's output rounding is the only one left.
+template <int KS, bool SPLIT = false>
+__device__ __forceinline__ void slot_rank_mfma(sf32x4 (&acc)[2 * KS], const char* img, sbf16x8 a, int lane,
+                                               sbf16x8 a_lo = sbf16x8{}) {
     using I = SlotImg<KS>;
     const int i = lane & 15, g = lane >> 4;
     const char* p0 = img + (4 * g + (i >> 2)) * I::PITCH + (i & 3) * 8;
@@ -410,6 +415,7 @@ __device__ __forceinline__ void slot_rank_mfma(sf32x4 (&acc)[2 * KS], const char
         f.t[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ss16x4*)(p0 + ct * 32));
         f.t[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ss16x4*)(p0 + 16 * I::PITCH + ct * 32));
         acc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, f.v, acc[ct], 0, 0, 0);
+        if constexpr (SPLIT) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_lo, f.v, acc[ct], 0, 0, 0);
     }
 }
 // the 4 waves' [16 slots][D (+1)] accumulators meet in LDS (each wave writes into its own image), summed into partial
@@ -478,7 +484,7 @@ __global__ __launch_bounds__(256) void slot_fwd_mfma_kernel(const bf16_t* __rest
         // hand-issued loads younger than the one awaited (see the note on counting above)
         constexpr int AFTER_V = DEEP ? 2 * KS : 0;               // step 0 only: the next step's k fragments
         const int later = (DEEP && step == 0) ? AFTER_V : 0;
-        SPk8 af;
+        SPk8 af, al;
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
             const int nt = n0 + step * 32 + half * 16;          // first row of the 16-row tile
@@ -507,6 +513,9 @@ __global__ __launch_bounds__(256) void slot_fwd_mfma_kernel(const bf16_t* __rest
                 const float ae = ok ? a + eps : 0.f;
                 cs += ae;
                 af.e[4 * half + r] = f32_to_bf16(ae);
+                // (what the rounding took away, exact in fp32: with few rows per slot nothing averages the operand's
+                // rounding out, and updates would carry it on top of its own -- 1.5 U of w^T |v| measured at N = 15)
+                al.e[4 * half + r] = f32_to_bf16(ae - bf16_to_f32(af.e[4 * half + r]));
             }
         }
         if (later) slot_wait<FULL, AFTER_V>(); else slot_wait<FULL, 0>();
@@ -515,7 +524,7 @@ __global__ __launch_bounds__(256) void slot_fwd_mfma_kernel(const bf16_t* __rest
             if (!DEEP) issue_k(1);
             issue_v(1);
         }
-        slot_rank_mfma<KS>(U, img, af.v, lane);
+        slot_rank_mfma<KS, true>(U, img, af.v, lane, al.v);
     }
     cs += __shfl_xor(cs, 16, 64);
     cs += __shfl_xor(cs, 32, 64);
@@ -920,7 +929,36 @@ inline bool slot_mfma_ok(const void* a, const void* b, const void* c, int64_t kv
 inline int nchunks(int N) { return (N + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK; }
 inline int nchunks_mfma(int N) { return (N + MROWS - 1) / MROWS; }
 
+// The dispatch decision of focus_slot_attn_fwd / focus_slot_attn_bwd, in one place (focus_slot_attn_route reports it).
+struct SlotRoute { int kernel, full, ks, kp, dv; };
+inline int slot_route(bool backward, const void* k_t, const void* v_t, int64_t kv_bs, const void* q, const void* dk_t,
+                      const void* dv_t, const void* wl, int N, int K, int D, int dtype, SlotRoute& r) {
+    if (backward && wl && !focus_slot_kv_grad_ok(K, D, dtype, 1)) return FOCUS_ERR_SHAPE;
+    if (N <= 0 || K <= 0 || K > 32 || D <= 0 || D > 256) return FOCUS_ERR_SHAPE;
+    const bool mfma = slot_mfma_ok(k_t, v_t, q, kv_bs, K, D, dtype);
+    if (backward && wl && !(mfma && focus_aligned(wl, 16))) return FOCUS_ERR_ALIGN;
+    r = SlotRoute{0, 0, 0, 0, 0};
+    if (mfma && (!backward || wl || (focus_aligned(dk_t, 8) && focus_aligned(dv_t, 8)))) {
+        r.kernel = !backward ? FOCUS_SLOT_KERNEL_FWD_MFMA : wl ? FOCUS_SLOT_KERNEL_BWD_DEFER : FOCUS_SLOT_KERNEL_BWD_MFMA;
+        r.ks = D / 32;
+        r.full = (!backward || wl) && N % MROWS == 0 && slot_hand_loads();
+        return FOCUS_OK;
+    }
+    r.kernel = backward ? FOCUS_SLOT_KERNEL_BWD_GENERIC : FOCUS_SLOT_KERNEL_FWD_GENERIC;
+    r.dv = (D + 63) / 64;
+    r.kp = K <= 4 ? 4 : K <= 8 ? 8 : K <= 16 ? 16 : 32;
+    return FOCUS_OK;
+}
+
 }  // namespace
+
+extern "C" int focus_slot_attn_route(int backward, const void* k_t, const void* v_t, int64_t kv_bs, const void* q,
+                                     const void* dk_t, const void* dv_t, const void* wl, int N, int K, int D, int dtype) {
+    SlotRoute r;
+    const int st = slot_route(backward != 0, k_t, v_t, kv_bs, q, dk_t, dv_t, wl, N, K, D, dtype, r);
+    if (st != FOCUS_OK) return st;
+    return r.kernel | r.full << 8 | (r.ks ? r.ks : r.kp) << 16 | r.dv << 24;
+}
 
 extern "C" size_t focus_slot_attn_workspace_bytes(int B, int N, int K, int D) {
     return (size_t)B * nchunks(N) * K * (D + 1) * sizeof(float);     // nchunks(N) >= nchunks_mfma(N)
@@ -928,8 +966,7 @@ extern "C" size_t focus_slot_attn_workspace_bytes(int B, int N, int K, int D) {
 
 #define SLOT_DISPATCH(KERNEL_CALL)                                                          \
     do {                                                                                    \
-        const int dv = (D + 63) / 64;                                                       \
-        const int kp = K <= 4 ? 4 : K <= 8 ? 8 : K <= 16 ? 16 : 32;                         \
+        const int dv = route.dv, kp = route.kp;                                             \
         bool done = false;                                                                  \
         SLOT_CASE(4, 1) SLOT_CASE(4, 2) SLOT_CASE(4, 3) SLOT_CASE(4, 4)                     \
         SLOT_CASE(8, 1) SLOT_CASE(8, 2) SLOT_CASE(8, 3) SLOT_CASE(8, 4)                     \
@@ -945,10 +982,13 @@ extern "C" int focus_slot_attn_fwd(const void* k_t, const void* v_t, int64_t kv_
     if (B <= 0 || N <= 0 || K <= 0 || K > 32 || D <= 0 || D > 256 || B > 65535) return FOCUS_ERR_SHAPE;
     if (partial_bytes < focus_slot_attn_workspace_bytes(B, N, K, D)) return FOCUS_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    if (slot_mfma_ok(k_t, v_t, q, kv_bs, K, D, dtype)) {
+    SlotRoute route;
+    const int rs = slot_route(false, k_t, v_t, kv_bs, q, nullptr, nullptr, nullptr, N, K, D, dtype, route);
+    if (rs != FOCUS_OK) return rs;
+    if (route.kernel == FOCUS_SLOT_KERNEL_FWD_MFMA) {
         dim3 gm(nchunks_mfma(N), B);
 #define SFM_(KS, FULL) hipLaunchKernelGGL((slot_fwd_mfma_kernel<KS, FULL>), gm, dim3(256), 0, s, (const bf16_t*)k_t, (const bf16_t*)v_t, kv_bs, (const bf16_t*)q, (bf16_t*)attn_vis, attn_bs, (float*)partial, N, K, eps)
-#define SFM(KS) do { if (N % MROWS == 0 && slot_hand_loads()) SFM_(KS, true); else SFM_(KS, false); } while (0)
+#define SFM(KS) do { if (route.full) SFM_(KS, true); else SFM_(KS, false); } while (0)
         if (D == 64) SFM(2); else if (D == 128) SFM(4); else if (D == 192) SFM(6); else SFM(8);
 #undef SFM
 #undef SFM_
@@ -959,7 +999,7 @@ extern "C" int focus_slot_attn_fwd(const void* k_t, const void* v_t, int64_t kv_
         return FOCUS_OK;
     }
     dim3 grid(nchunks(N), B);
-    const size_t lds = ((size_t)K * D + 256) * sizeof(float);
+    const size_t lds = ((size_t)K * D + 256) * sizeof(float);             // <= 33,792 bytes at K = 32, D = 256
 #define SLOT_CASE(KP_, DV_)                                                                                   \
     if (!done && kp == KP_ && dv == DV_) {                                                                    \
         done = true;                                                                                          \
@@ -996,13 +1036,15 @@ extern "C" int focus_slot_attn_bwd(const void* k_t, const void* v_t, int64_t kv_
     if (B <= 0 || N <= 0 || K <= 0 || K > 32 || D <= 0 || D > 256 || B > 65535) return FOCUS_ERR_SHAPE;
     if (partial_bytes < focus_slot_attn_workspace_bytes(B, N, K, D)) return FOCUS_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    if (wl && !(slot_mfma_ok(k_t, v_t, q, kv_bs, K, D, dtype) && focus_aligned(wl, 16))) return FOCUS_ERR_ALIGN;
-    if (slot_mfma_ok(k_t, v_t, q, kv_bs, K, D, dtype) && (wl || (focus_aligned(dk_t, 8) && focus_aligned(dv_t, 8)))) {
+    SlotRoute route;
+    const int rs = slot_route(true, k_t, v_t, kv_bs, q, dk_t, dv_t, wl, N, K, D, dtype, route);
+    if (rs != FOCUS_OK) return rs;
+    if (route.kernel != FOCUS_SLOT_KERNEL_BWD_GENERIC) {
         dim3 gm(nchunks_mfma(N), B);
 #define SBD(KS, FULL, DA) hipLaunchKernelGGL((slot_bwd_defer_kernel<KS, FULL, DA>), gm, dim3(256), 0, s, (const bf16_t*)k_t, (const bf16_t*)v_t, kv_bs, (const bf16_t*)attn_vis, attn_bs, colsum, (const bf16_t*)upd, (const bf16_t*)dupd, (const bf16_t*)dattn_vis, (bf16_t*)wl, (float*)partial, N, K, eps)
 #define SBM(KS) do { \
         if (wl) { \
-            if (N % MROWS == 0 && slot_hand_loads()) { if (dattn_vis) SBD(KS, true, true); else SBD(KS, true, false); } \
+            if (route.full) { if (dattn_vis) SBD(KS, true, true); else SBD(KS, true, false); } \
             else { if (dattn_vis) SBD(KS, false, true); else SBD(KS, false, false); } } \
         else hipLaunchKernelGGL((slot_bwd_mfma_kernel<KS>), gm, dim3(256), 0, s, (const bf16_t*)k_t, (const bf16_t*)v_t, kv_bs, (const bf16_t*)q, (const bf16_t*)attn_vis, attn_bs, colsum, (const bf16_t*)upd, (const bf16_t*)dupd, (const bf16_t*)dattn_vis, (bf16_t*)dk_t, (bf16_t*)dv_t, accumulate, (float*)partial, N, K, eps); } while (0)
         if (D == 64) SBM(2); else if (D == 128) SBM(4); else if (D == 192) SBM(6); else SBM(8);
@@ -1015,10 +1057,14 @@ extern "C" int focus_slot_attn_bwd(const void* k_t, const void* v_t, int64_t kv_
         return FOCUS_OK;
     }
     dim3 grid(nchunks(N), B);
-    const size_t lds = ((size_t)2 * K * D + 64 + 256) * sizeof(float);
+    const size_t lds = ((size_t)2 * K * D + 64 + 256) * sizeof(float);    // 66,816 bytes at K = 32, D = 256: above 64 KiB
+#define SLOT_BIG_LDS(T_, KP_, DV_) do { if (lds > 64 * 1024) { \
+        static bool once = (hipFuncSetAttribute((const void*)slot_bwd_kernel<T_, KP_, DV_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess); \
+        (void)once; } } while (0)
 #define SLOT_CASE(KP_, DV_)                                                                                    \
     if (!done && kp == KP_ && dv == DV_) {                                                                     \
         done = true;                                                                                           \
+        if (dtype == FOCUS_BF16) SLOT_BIG_LDS(bf16_t, KP_, DV_); else SLOT_BIG_LDS(float, KP_, DV_);           \
         if (dtype == FOCUS_BF16)                                                                               \
             hipLaunchKernelGGL((slot_bwd_kernel<bf16_t, KP_, DV_>), grid, dim3(256), lds, s, (const bf16_t*)k_t, \
                                (const bf16_t*)v_t, kv_bs, (const bf16_t*)q, (const bf16_t*)attn_vis, attn_bs,  \
@@ -1032,6 +1078,7 @@ extern "C" int focus_slot_attn_bwd(const void* k_t, const void* v_t, int64_t kv_
     }
     SLOT_DISPATCH();
 #undef SLOT_CASE
+#undef SLOT_BIG_LDS
     FOCUS_CHECK_LAUNCH();
     if (dtype == FOCUS_BF16)
         hipLaunchKernelGGL((slot_bwd_finish<bf16_t>), dim3(K, B), dim3(64 * FIN_CL), 0, s, (const float*)partial, (bf16_t*)dq,

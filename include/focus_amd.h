@@ -374,6 +374,21 @@ int focus_slot_attn_bwd(const void* k_t, const void* v_t, int64_t kv_bstride, co
  * products with the iterations stacked along the reduction).  bf16, K <= 16, D in {64,128,192,256}.  dk_t / dv_t rows are
  * kv_ld elements apart (>= D): with dv_t = dk_t + D and kv_ld = 2 D the two gradients form one [B,N,2D] matrix [dk | dv],
  * which lets the projections' backward run as one product each (d(input) = [dk|dv].[Wk;Wv], d[Wk;Wv] = [dk|dv]^T.x). */
+/* Which kernel focus_slot_attn_fwd (backward == 0) or focus_slot_attn_bwd (backward != 0) launches for these arguments:
+ * the entry points take their decision from the same host function, nothing is launched here (no GPU needed).  For the
+ * forward pass dk_t, dv_t and wl as NULL.  Returns a negative status where the entry point would refuse (FOCUS_ERR_SHAPE,
+ * FOCUS_ERR_ALIGN), else   kernel | full << 8 | p0 << 16 | p1 << 24   with kernel one of focus_slot_kernel, full = 1 for
+ * the FULL instantiation (every row of every workgroup exists: hand-issued loads), p0 = KS (= D / 32) of the MFMA kernels
+ * or KP (slots padded to 4, 8, 16, 32) of the generic ones, p1 = DV (= ceil(D / 64)) of the generic ones, else 0. */
+enum focus_slot_kernel {
+    FOCUS_SLOT_KERNEL_FWD_MFMA = 1,      /* slot_fwd_mfma_kernel<KS, FULL>            */
+    FOCUS_SLOT_KERNEL_FWD_GENERIC = 2,   /* slot_fwd_kernel<T, KP, DV>                */
+    FOCUS_SLOT_KERNEL_BWD_DEFER = 3,     /* slot_bwd_defer_kernel<KS, FULL, HAS_DA>   */
+    FOCUS_SLOT_KERNEL_BWD_MFMA = 4,      /* slot_bwd_mfma_kernel<KS>                  */
+    FOCUS_SLOT_KERNEL_BWD_GENERIC = 5    /* slot_bwd_kernel<T, KP, DV>                */
+};
+int focus_slot_attn_route(int backward, const void* k_t, const void* v_t, int64_t kv_bstride, const void* q,
+                          const void* dk_t, const void* dv_t, const void* wl, int N, int K, int D, int dtype);
 int focus_slot_kv_grad_ok(int K, int D, int dtype, int iters);
 int focus_slot_kv_grad(const void* wl0, const void* wl1, const void* wl2, const void* wl3, const void* q0, const void* q1,
                        const void* q2, const void* q3, const void* du0, const void* du1, const void* du2, const void* du3,
