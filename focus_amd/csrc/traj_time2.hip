@@ -620,9 +620,13 @@ __global__ __launch_bounds__(256) void time2_dlg_kernel(const bf16_t* __restrict
 #pragma unroll
         for (int f = 0; f < FT; ++f) sdl[rl][f][h] = scale * a[f] * (da[f] - dot);
     }
-    if (tid < RPB * GPR && cg < MAXH - HEADS) {                      // padded head columns: zeros (read by time2_dx_kernel)
+    // padded head columns: zeros (time2_dx_kernel reads all 16 as an MFMA operand).  Strided over the row's threads: with
+    // one head a row has 8 threads for 15 columns
+    if (tid < RPB * GPR) {
+        for (int p = cg; p < MAXH - HEADS; p += GPR) {
 #pragma unroll
-        for (int f = 0; f < FT; ++f) sdl[rl][f][HEADS + cg] = 0.f;
+            for (int f = 0; f < FT; ++f) sdl[rl][f][HEADS + p] = 0.f;
+        }
     }
     __syncthreads();
     // dl row -> HBM (bf16 [row][f][16]): FT * 16 values per row, 8 per thread

@@ -238,7 +238,13 @@ int focus_traj_time_bwd(const void* q2, const void* k2, const void* xt, const fl
  *        ws: focus_traj_time2_workspace_bytes() bytes of scratch.
  *   bwd: dxt [B,S,F,C] (fully written: a*dout + sum_h dl*u); g [h,B*S,C] bf16 = d(loss)/d(u), head-major so that each
  *        head's slice is a dense matrix, from which the caller forms  dq2[:, h*64+dd] = sum_c g[h,:,c] Wk[h*64+dd, c]
- *        and  dWk[h*64+dd, c] = sum_s q2[s,h*64+dd] g[h,s,c]  (two batched GEMMs over the heads); dl [B,S,F,16] bf16 scratch.  proj_kv.bias gets its exact zero gradient. */
+ *        and  dWk[h*64+dd, c] = sum_s q2[s,h*64+dd] g[h,s,c]  (two batched GEMMs over the heads); dl [B,S,F,16] bf16 scratch
+ *        (columns heads..15 are written as +0).  proj_kv.bias gets its exact zero gradient.
+ * Status, judged in this order before any launch (pinned by tests/test_gpu_traj_time2.py; a refused call writes nothing):
+ *   FOCUS_ERR_NULL (any pointer); FOCUS_ERR_SHAPE (B <= 0, S <= 0, F not in {4, 8, 16}, heads outside 1..16, d != 64, a
+ *   dtype other than FOCUS_BF16, ldw < C, ldw % 8 != 0, a batch stride below S*C or not a multiple of 8);
+ *   FOCUS_ERR_ALIGN (a pointer not 16-byte aligned); FOCUS_ERR_WORKSPACE (fwd: ws_bytes below
+ *   focus_traj_time2_workspace_bytes(), which is 0 for a non-positive size or d != 64). */
 size_t focus_traj_time2_workspace_bytes(int B, int S, int F, int heads, int d);
 int focus_traj_time2_fwd(const void* q2, const void* xt, const void* wkT, int64_t ldw, void* out, int64_t out_bstride,
                          float* attn2, void* ws, size_t ws_bytes, int B, int S, int F, int heads, int d, int dtype,
@@ -635,7 +641,10 @@ int focus_greedy_next(const void* logits, int64_t ldl, const float* dict, const 
 /* Both consumers of g = d(loss)/d(u) of the re-associated temporal step in one pass over g (traj_time2_gw.hip; autograd of
  * attention.py:536-549): dq2[r, h*d+dd] = sum_c g[h,r,c] Wk[h*d+dd, c] and dWk[h*d+dd, c] = sum_r q2[r, h*d+dd] g[h,r,c].
  * g [heads][R][C] bf16, q2 / dq2 [R][C] bf16, wk = the bf16 rows of Wk (row stride wk_ld), dwk [C][C] fp32 dense.
- * bf16, d = 64, C = 768, R % 32 == 0 (focus_traj_time2_gw_ok); ws: focus_traj_time2_gw_workspace_bytes. */
+ * bf16, d = 64, C = 768, R % 32 == 0 (focus_traj_time2_gw_ok); ws: focus_traj_time2_gw_workspace_bytes.
+ * Status, in this order before any launch (a refused call writes nothing): FOCUS_ERR_NULL (any pointer); FOCUS_ERR_SHAPE
+ * (not focus_traj_time2_gw_ok, wk_ld % 8 != 0); FOCUS_ERR_ALIGN (g, q2, wk or dwk not 16-byte aligned);
+ * FOCUS_ERR_WORKSPACE (ws_bytes too small). */
 int focus_traj_time2_gw_ok(int R, int heads, int d, int dtype);
 size_t focus_traj_time2_gw_workspace_bytes(int R, int heads, int d);
 int focus_traj_time2_gw(const void* g, const void* q2, const void* wk, int64_t wk_ld, void* dq2, float* dwk, void* ws,
