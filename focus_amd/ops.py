@@ -3032,6 +3032,87 @@ def clip_sample(clips, params, out_h, out_w, mean, std, reverse=False, dtype=tor
 
 
 # --------------------------------------------------------------------------------------------------
+# clip sampling with a colour stage: the AVA front end (clip_color.hip)
+# --------------------------------------------------------------------------------------------------
+COLOR_BRIGHTNESS, COLOR_CONTRAST, COLOR_SATURATION = 0, 1, 2          # enum focus_color_op
+
+
+def clip_colors(colors, n_clips):
+    """The host image of the focus_clip_color table: int32 [n, 10] (n_ops, op[3], then alpha[3] and shift[3] as float bits).
+    colors: one mapping per clip with `op` (0..3 kinds of COLOR_*, applied in this order), `alpha` (one weight per op) and
+    `shift` (three floats by source channel).  More than three ops, an unknown or repeated kind, or an alpha / shift that is
+    not finite is a ValueError: the kernels cannot report it.  Needs no device."""
+    import math
+    import numpy as np
+    if len(colors) != n_clips:
+        raise ValueError("focus_amd: clip_sample_color takes one colour record per clip (%d for %d clips)" % (len(colors), n_clips))
+    rec = np.zeros((n_clips, 10), dtype=np.int32)
+    flt = rec.view(np.float32)
+    for i, c in enumerate(colors):
+        op, alpha, shift = [int(k) for k in c["op"]], [float(a) for a in c["alpha"]], [float(s) for s in c["shift"]]
+        if len(op) > 3 or len(alpha) != len(op):
+            raise ValueError("focus_amd: clip %d: %d colour ops with %d weights (at most three, one weight each)" % (i, len(op), len(alpha)))
+        if any(k not in (COLOR_BRIGHTNESS, COLOR_CONTRAST, COLOR_SATURATION) for k in op) or len(set(op)) != len(op):
+            raise ValueError("focus_amd: clip %d: colour ops %r (each of brightness 0, contrast 1, saturation 2 at most once)" % (i, op))
+        if len(shift) != 3 or not all(math.isfinite(v) for v in alpha + shift):
+            raise ValueError("focus_amd: clip %d: alpha %r / shift %r (finite, three shifts)" % (i, alpha, shift))
+        rec[i, 0] = len(op)
+        rec[i, 1:1 + len(op)] = op
+        flt[i, 4:4 + len(op)] = alpha
+        flt[i, 7:10] = shift
+    return rec
+
+
+def clip_sample_color(clips, params, colors, out_h, out_w, mean, std, gray_w, reverse=False, dtype=torch.float32, layout="BCTHW"):
+    """clip_sample with the colour stage of the AVA pipeline between /255 and the normalisation: per clip the ops of its
+    record (clip_colors) in the record's order -- brightness x*a, saturation x*a + g*(1-a) with g the pixel's grey, contrast
+    x*a + m_t*(1-a) with m_t the mean grey of output frame t as it stands when contrast runs -- then + shift, mean / std,
+    the reversal and the cast.  gray_w, shift, mean and std go by SOURCE channel.  One pinned H2D copy carries both tables;
+    focus_clip_gray_mean runs only when some record holds contrast, then focus_clip_sample_color: at most two launches.
+    No CPU fallback."""
+    import numpy as np
+    if layout not in ("BCTHW", "BTCHW"):
+        raise ValueError("focus_amd: clip_sample_color layout is BCTHW or BTCHW (got %r)" % (layout,))
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError("focus_amd: unsupported dtype %s (float32 or bfloat16)" % dtype)
+    if out_h < 1 or out_w < 1:
+        raise ValueError("focus_amd: clip_sample_color output size %dx%d" % (out_h, out_w))
+    if len(mean) != 3 or len(std) != 3 or any(float(s) == 0.0 for s in std):
+        raise ValueError("focus_amd: clip_sample_color takes three means and three non-zero stds")
+    if len(gray_w) != 3 or not all(np.isfinite(float(w)) for w in gray_w):
+        raise ValueError("focus_amd: clip_sample_color takes three finite grey weights")
+    if len(clips) != len(params) or not clips:
+        raise ValueError("focus_amd: clip_sample_color takes one parameter set per clip and at least one clip")
+    col = clip_colors(colors, len(clips))
+    rec = clip_items(clips, params, out_h, out_w)
+    dev, B, T = clips[0].device, len(clips), int(clips[0].shape[0])
+    plane = out_h * out_w
+    if layout == "BCTHW":
+        out = torch.empty(B, 3, T, out_h, out_w, device=dev, dtype=dtype)
+        sc, st = T * plane, plane
+    else:
+        out = torch.empty(B, T, 3, out_h, out_w, device=dev, dtype=dtype)
+        sc, st = plane, 3 * plane
+    f3 = lambda v: ctypes.cast((ctypes.c_float * 3)(*[float(x) for x in v]), ctypes.c_void_p)
+    keep = [f3(mean), f3(std), f3(gray_w)]
+    contrast = bool(((col[:, 1:4] == COLOR_CONTRAST) & (np.arange(3)[None] < col[:, :1])).any())
+    table = np.concatenate([rec.view(np.uint8).reshape(-1), col.view(np.uint8).reshape(-1)])      # items (72 B each), then colours
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        tab = torch.from_numpy(table).pin_memory().to(dev, non_blocking=True)
+        items, cols = tab.data_ptr(), tab.data_ptr() + rec.nbytes
+        frame_mean = torch.empty(B * T, device=dev, dtype=torch.float32)      # read only for clips with contrast
+        if contrast:
+            nbytes = int(L.focus_clip_color_workspace_bytes(B, T, out_h, out_w))
+            ws = torch.empty(max(nbytes, 4), device=dev, dtype=torch.uint8)
+            _lib.check(L.focus_clip_gray_mean(items, cols, B, T, out_h, out_w, keep[2], _p(frame_mean), _p(ws), nbytes, _stream()),
+                       "clip_gray_mean")
+        _lib.check(L.focus_clip_sample_color(items, cols, _p(frame_mean), B, T, out_h, out_w, _p(out), 3 * T * plane, sc, st,
+                                             keep[0], keep[1], keep[2], int(bool(reverse)), _dt(out), _stream()), "clip_sample_color")
+    return out
+
+
+# --------------------------------------------------------------------------------------------------
 # Mixup / CutMix on the device (datasets/mixup.py:40-192) and the soft-target loss (losses.py:15-36): csrc/mixup.hip
 # --------------------------------------------------------------------------------------------------
 def _need_dense(x, what):

@@ -134,7 +134,10 @@ def _defaults():
                           INPUT_CHANNEL_NUM=[3, 3], STD=[0.225, 0.225, 0.225], TRAIN_JITTER_SCALES=[256, 320],
                           TRAIN_CROP_SIZE=224, TEST_CROP_SIZE=256, RANDOM_FLIP=True, REVERSE_INPUT_CHANNEL=False,
                           # the multi-label route (defaults.py:679-682 of the reference): BCE losses, mAP, "sum" / "max" views
-                          MULTI_LABEL=False, ENSEMBLE_METHOD="sum"))
+                          MULTI_LABEL=False, ENSEMBLE_METHOD="sum",
+                          # AlexNet PCA lighting of the AVA route (defaults.py:616-624 of the reference; RGB based)
+                          TRAIN_PCA_EIGVAL=[0.225, 0.224, 0.229],
+                          TRAIN_PCA_EIGVEC=[[-0.5675, 0.7192, 0.4009], [-0.5808, -0.0045, -0.8140], [-0.5836, -0.6948, 0.4203]]))
     C.SLOTS_OPTIM = CfgNode(dict(DVAE=3e-4, ENC=1e-4, DEC=4e-4, HALF_LIFE=100000, WARMUP_STEPS=20000, CLIP=1.0,
                                  TAU_START=1.0, TAU_FINAL=0.1, TAU_STEPS=30000, STEPS=200000, STEP_INTERVAL=5000))
     C.SOLVER = CfgNode(dict(BASE_LR=0.1, ORVIT_BASE_LR=-1.0, LR_POLICY="cosine", COSINE_END_LR=0.0, GAMMA=0.1,
@@ -152,7 +155,10 @@ def _defaults():
     # what AVAMeter and ava_helper.load_image_lists read (defaults.py:917-974 of the reference; its directories name one machine)
     C.AVA = CfgNode(dict(FRAME_DIR="", FRAME_LIST_DIR="", ANNOTATION_DIR="", TRAIN_LISTS=["train.csv"], TEST_LISTS=["val.csv"],
                          FULL_TEST_ON_VAL=False, LABEL_MAP_FILE="ava_action_list_v2.2_for_activitynet_2019.pbtxt",
-                         EXCLUSION_FILE="ava_val_excluded_timestamps_v2.2.csv", GROUNDTRUTH_FILE="ava_val_v2.2.csv"))
+                         EXCLUSION_FILE="ava_val_excluded_timestamps_v2.2.csv", GROUNDTRUTH_FILE="ava_val_v2.2.csv",
+                         # what datasets/device_sampling.sample_ava_clips reads (defaults.py:950-980 of the reference)
+                         BGR=False, TRAIN_USE_COLOR_AUGMENTATION=False, TRAIN_PCA_JITTER_ONLY=True, TEST_FORCE_FLIP=False,
+                         CENTER_CROP_TEST=True, IMG_PROC_BACKEND="cv2"))
     C.DATA_LOADER = CfgNode(dict(NUM_WORKERS=8, PIN_MEMORY=True, ENABLE_MULTI_THREAD_DECODE=False))
     C.TENSORBOARD = CfgNode(dict(ENABLE=True))
     C.NUM_GPUS = 1

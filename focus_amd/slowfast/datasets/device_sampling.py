@@ -8,25 +8,34 @@ reference's random numbers and moves the boxes (`sampling_params`, bit-identical
 produces the pixels of the whole batch (`ops.clip_sample`).  RandAugment runs in front of it, on the uint8 clips and on the
 device too (`augment_clips`: the host draws the reference's numbers and moves the boxes, `ops.randaug_apply` runs the ops),
 and random erasing behind it, in place on the sampled batch (`erase_clips`: the host draws the reference's rectangles, ONE
-`ops.random_erase_` writes them).  `make_batch` chains the three.  That is every augmentation the reference's video datasets
-apply: AUG.COLOR_JITTER is read by its ImageNet dataset alone (imagenet.py:136)."""
+`ops.random_erase_` writes them).  `make_batch` chains the three.  That is every augmentation the reference's SSv2, Kinetics,
+EPIC-Kitchens and STEVE datasets apply: AUG.COLOR_JITTER is read by its ImageNet dataset alone (imagenet.py:136).
+
+AVA is the one video dataset that does jitter colours (ava_dataset.py:255-365): normalised boxes in, [K,5] box rows out, and
+between /255 and the normalisation transform.color_jitter (brightness, contrast towards each frame's own mean grey,
+saturation, in a drawn order) and transform.lighting_jitter (PCA shift).  `sample_ava_clips` is its hand-off: the host plans
+(`sampling_params` for the geometry, `transform.color_plan` for the colours, the reference's draws in its order) and
+`ops.clip_sample_color` runs the batch in at most two launches (clip_color.hip)."""
 import math
 
 import numpy as np
 import torch
 
 from ... import ops
+from ..utils import box_ops
 from . import transform
 from .random_erasing import RandomErasing
 from .utils import boxes_to_orvit_format
 
 
 def sampling_params(height, width, spatial_idx=-1, min_scale=256, max_scale=320, crop_size=224, random_horizontal_flip=True,
-                    inverse_uniform_sampling=False, aspect_ratio=None, scale=None, boxes=None):
+                    inverse_uniform_sampling=False, aspect_ratio=None, scale=None, boxes=None, crop=True):
     """What datasets/utils.py:111-188 `spatial_sampling` would do to a [T,3,height,width] clip, without touching a pixel.
     Consumes exactly the reference's draws for the chosen mode, in its order (numpy's and Python's global generators).
     Returns (params, boxes): params holds the descriptor fields of ops.clip_sample (sy0, sx0, sh, sw, rh, rw, oy0, ox0, flip)
-    and out_h, out_w; boxes (numpy xyxy pixels, or None) are the reference's transformed boxes, bit for bit."""
+    and out_h, out_w; boxes (numpy xyxy pixels, or None) are the reference's transformed boxes, bit for bit.  crop=False
+    (the test views only) stops after the short-side resize: the window is the whole resized frame (AVA's test split without
+    AVA.CENTER_CROP_TEST)."""
     assert spatial_idx in [-1, 0, 1, 2]
     p = dict(sy0=0, sx0=0, sh=height, sw=width, rh=height, rw=width, oy0=0, ox0=0, flip=0, out_h=crop_size, out_w=crop_size)
     if spatial_idx == -1 and not (aspect_ratio is None and scale is None):
@@ -64,6 +73,9 @@ def sampling_params(height, width, spatial_idx=-1, min_scale=256, max_scale=320,
                     y_offset = int(np.random.randint(0, rh - crop_size))
                 if rw > crop_size:
                     x_offset = int(np.random.randint(0, rw - crop_size))
+        elif not crop:
+            p.update(rh=rh, rw=rw, out_h=rh, out_w=rw)
+            return p, boxes
         else:                                                     # transform.uniform_crop
             y_offset = int(math.ceil((rh - crop_size) / 2))
             x_offset = int(math.ceil((rw - crop_size) / 2))
@@ -125,6 +137,99 @@ def sample_clips(cfg, clips_u8, boxes, spatial_idx=-1, min_scale=None, max_scale
                                  dtype, "BCTHW")
     # one hand-off for the batch: boxes_to_orvit_format works box by box, so this is what B calls would give
     return inputs, boxes_to_orvit_format(np.stack(out_boxes), crop_size, crop_size)
+
+
+GRAY_BGR = (0.114, 0.587, 0.299)                                  # transform.grayscale by BGR position
+
+
+def ava_plan(cfg, height, width, boxes, split):
+    """What ava_dataset.py:268-365 (`_images_and_boxes_preprocessing`, the "pytorch" backend) would do to a [T,3,height,width]
+    clip and its normalised boxes [n,4], without touching a pixel.  Consumes the reference's draws in its order: scale, crop y,
+    crop x, flip (train; the flip is always drawn, DATA.RANDOM_FLIP is not read there), the one scale draw of val / test and the
+    flip draw of AVA.TEST_FORCE_FLIP, then for train under AVA.TRAIN_USE_COLOR_AUGMENTATION the permutation and three alphas
+    (unless AVA.TRAIN_PCA_JITTER_ONLY) and the PCA normal.  Returns (params, color, boxes): the fields of ops.clip_sample_color
+    (color.shift by BGR position) and the reference's boxes in pixels of the output, bit for bit."""
+    data, ava = cfg.DATA, cfg.AVA
+    boxes = np.array(boxes)
+    boxes[:, [0, 2]] *= width
+    boxes[:, [1, 3]] *= height
+    boxes = transform.clip_boxes_to_image(boxes, height, width)
+    if split == "train":
+        lo, hi = data.TRAIN_JITTER_SCALES
+        p, boxes = sampling_params(height, width, -1, lo, hi, data.TRAIN_CROP_SIZE, True, boxes=boxes)
+    elif split in ("val", "test"):
+        size = data.TEST_CROP_SIZE
+        # the reference reads self.AVA.CENTER_CROP_TEST in the test split (an AttributeError); cfg.AVA.CENTER_CROP_TEST is meant
+        crop = split == "val" or bool(ava.CENTER_CROP_TEST)
+        p, boxes = sampling_params(height, width, 1, size, size, size, boxes=boxes, crop=crop)
+        if ava.TEST_FORCE_FLIP:                                   # transform.horizontal_flip(1, ...): the draw is made
+            flipped = boxes.copy()
+            if np.random.uniform() < 1:
+                p["flip"] = 1
+                flipped[:, [0, 2]] = p["out_w"] - boxes[:, [2, 0]] - 1
+            boxes = flipped
+    else:
+        raise NotImplementedError("{} split not supported yet!".format(split))
+    color = dict(op=[], alpha=[], shift=[0.0, 0.0, 0.0])
+    if split == "train" and ava.TRAIN_USE_COLOR_AUGMENTATION:
+        var = 0 if ava.TRAIN_PCA_JITTER_ONLY else 0.4
+        color = transform.color_plan(var, var, var, 0.1, np.array(data.TRAIN_PCA_EIGVAL).astype(np.float32),
+                                     np.array(data.TRAIN_PCA_EIGVEC).astype(np.float32))
+    return p, color, transform.clip_boxes_to_image(boxes, p["out_h"], p["out_w"])
+
+
+def sample_ava_clips(cfg, clips_u8, boxes, split, orvit_boxes=None, source_order="bgr"):
+    """The hand-off between decoding and the detection model for one AVA batch (ava_dataset.py:255-365 and 404-437).
+    clips_u8: list of uint8 [T,H,W,3] CUDA tensors (H, W may differ per clip) in `source_order` "bgr" (what the reference
+    decodes) or "rgb"; boxes: per clip a numpy [n_i,4] array of NORMALISED xyxy boxes; orvit_boxes: per clip [T,O,4]
+    normalised or None; split: "train" | "val" | "test".  Returns (inputs [B,3,T,S,S], meta): inputs are channel-ordered BGR
+    under AVA.BGR, else RGB, bf16 under TRAIN.MIXED_PRECISION; meta["boxes"] fp32 [K,5] (batch index, x1, y1, x2, y2 in output
+    pixels), meta["ori_boxes"] [K,5] the untouched normalised boxes, meta["orvit_bboxes"] [B,T,O,4] cxcywh in [0,1] with empty
+    boxes zeroed (when orvit_boxes were given).  DATA.MEAN / STD are indexed by BGR position, as in the reference; the grey
+    weights and the PCA shift follow the true colours of either source order.  The test split without AVA.CENTER_CROP_TEST
+    returns rh x rw frames: every clip of the batch must then resize to one size (ValueError otherwise).  The pixels are
+    those of AVA.IMG_PROC_BACKEND "pytorch" under either backend."""
+    if source_order not in ("bgr", "rgb"):
+        raise ValueError("sample_ava_clips: source_order is bgr or rgb (got %r)" % (source_order,))
+    if len(clips_u8) != len(boxes) or (orvit_boxes is not None and len(orvit_boxes) != len(clips_u8)):
+        raise ValueError("sample_ava_clips takes one box array (and one ORViT box array) per clip")
+    params, colors, det, ori, orv = [], [], [], [], []
+    for i, clip in enumerate(clips_u8):
+        T, H, W = int(clip.shape[0]), int(clip.shape[1]), int(clip.shape[2])
+        b = np.array(boxes[i])
+        if b.ndim != 2 or b.shape[1] != 4:
+            raise ValueError("sample_ava_clips: clip %d has boxes of shape %s" % (i, b.shape))
+        n = b.shape[0]
+        ori.append(np.concatenate([np.full((n, 1), float(i)), b], axis=1))
+        if orvit_boxes is not None:
+            ob = np.asarray(orvit_boxes[i])
+            if ob.ndim != 3 or ob.shape[0] != T or ob.shape[2] != 4:
+                raise ValueError("sample_ava_clips: clip %d has %d frames and ORViT boxes of shape %s" % (i, T, ob.shape))
+            b = np.concatenate([b, ob.reshape(-1, 4)], axis=0)
+        p, color, b = ava_plan(cfg, H, W, b, split)
+        params.append(p)
+        colors.append(color)
+        det.append(np.concatenate([np.full((n, 1), float(i)), b[:n]], axis=1))
+        if orvit_boxes is not None:
+            o = torch.from_numpy(b[n:].reshape(ob.shape))
+            o = o / torch.tensor([p["out_w"], p["out_h"], p["out_w"], p["out_h"]]).reshape(1, 1, 4)
+            orv.append(box_ops.zero_empty_boxes(box_ops.box_xyxy_to_cxcywh(o), mode="cxcywh").float())
+    out_h, out_w = params[0]["out_h"], params[0]["out_w"]
+    if any((p["out_h"], p["out_w"]) != (out_h, out_w) for p in params):
+        raise ValueError("sample_ava_clips: without AVA.CENTER_CROP_TEST the clips of a batch must resize to one size (got %s)"
+                         % sorted({(p["out_h"], p["out_w"]) for p in params}))
+    mean, std, gray = list(cfg.DATA.MEAN), list(cfg.DATA.STD), list(GRAY_BGR)
+    if source_order == "rgb":                                     # source channel c sits at BGR position 2 - c
+        mean, std, gray = mean[::-1], std[::-1], gray[::-1]
+        colors = [dict(c, shift=c["shift"][::-1]) for c in colors]
+    reverse = (source_order == "bgr") != bool(cfg.AVA.BGR)
+    dtype = torch.bfloat16 if cfg.TRAIN.MIXED_PRECISION else torch.float32
+    inputs = ops.clip_sample_color(clips_u8, params, colors, out_h, out_w, mean, std, gray, reverse, dtype, "BCTHW")
+    meta = {"boxes": torch.from_numpy(np.concatenate(det, axis=0).astype(np.float32)),
+            "ori_boxes": torch.from_numpy(np.concatenate(ori, axis=0).astype(np.float32))}
+    if orvit_boxes is not None:
+        meta["orvit_bboxes"] = torch.stack(orv)
+    return inputs, meta
 
 
 def augment_clips(cfg, clips_u8, boxes=None):

@@ -190,3 +190,121 @@ def create_random_augment(input_size, auto_augment=None, interpolation="bilinear
         if auto_augment.startswith("rand"):
             return rand_augment_transform(auto_augment, aa_params)
     raise NotImplementedError
+
+
+# ---- the colour stage of the AVA pipeline (transform.py:297-517): frames [T,C,H,W] in BGR order, values in [0,1] ----
+def blend(images1, images2, alpha):
+    """transform.py:297-310."""
+    return images1 * alpha + images2 * (1 - alpha)
+
+
+def grayscale(images):
+    """transform.py:313-332: R 0.299, G 0.587, B 0.114 of a BGR clip, repeated over the three channels."""
+    img_gray = images.clone()
+    gray_channel = 0.299 * images[:, 2] + 0.587 * images[:, 1] + 0.114 * images[:, 0]
+    img_gray[:, 0] = gray_channel
+    img_gray[:, 1] = gray_channel
+    img_gray[:, 2] = gray_channel
+    return img_gray
+
+
+def color_jitter(images, img_brightness=0, img_contrast=0, img_saturation=0):
+    """transform.py:335-367: the enabled ops in a drawn order (one np.random.permutation, then each op's own uniform)."""
+    jitter = []
+    if img_brightness != 0:
+        jitter.append("brightness")
+    if img_contrast != 0:
+        jitter.append("contrast")
+    if img_saturation != 0:
+        jitter.append("saturation")
+    if len(jitter) > 0:
+        order = np.random.permutation(np.arange(len(jitter)))
+        for idx in range(0, len(jitter)):
+            if jitter[order[idx]] == "brightness":
+                images = brightness_jitter(img_brightness, images)
+            elif jitter[order[idx]] == "contrast":
+                images = contrast_jitter(img_contrast, images)
+            elif jitter[order[idx]] == "saturation":
+                images = saturation_jitter(img_saturation, images)
+    return images
+
+
+def brightness_jitter(var, images):
+    """transform.py:370-386."""
+    alpha = 1.0 + np.random.uniform(-var, var)
+    return blend(images, torch.zeros_like(images), alpha)
+
+
+def contrast_jitter(var, images):
+    """transform.py:389-406: towards the mean grey of each frame ALONE (dim (1,2,3) of [T,C,H,W])."""
+    alpha = 1.0 + np.random.uniform(-var, var)
+    img_gray = grayscale(images)
+    img_gray[:] = torch.mean(img_gray, dim=(1, 2, 3), keepdim=True)
+    return blend(images, img_gray, alpha)
+
+
+def saturation_jitter(var, images):
+    """transform.py:409-425."""
+    alpha = 1.0 + np.random.uniform(-var, var)
+    return blend(images, grayscale(images), alpha)
+
+
+def _pca_rgb(alphastd, eigval, eigvec):
+    """The draw and the RGB shift of lighting_jitter (transform.py:444-450), in numpy float64 as there."""
+    alpha = np.random.normal(0, alphastd, size=(1, 3))
+    eig_vec = np.array(eigvec)
+    eig_val = np.reshape(eigval, (1, 3))
+    return np.sum(eig_vec * np.repeat(alpha, 3, axis=0) * np.repeat(eig_val, 3, axis=0), axis=1)
+
+
+def lighting_jitter(images, alphastd, eigval, eigvec):
+    """transform.py:428-473: AlexNet PCA lighting; the channel at BGR position idx gets rgb[2 - idx]."""
+    if alphastd == 0:
+        return images
+    rgb = _pca_rgb(alphastd, eigval, eigvec)
+    out_images = torch.zeros_like(images)
+    if images.dim() not in (3, 4):
+        raise NotImplementedError(f"Unsupported dimension {images.dim()}")
+    for idx in range(images.shape[images.dim() - 3]):
+        if images.dim() == 3:
+            out_images[idx] = images[idx] + rgb[2 - idx]
+        else:
+            out_images[:, idx] = images[:, idx] + rgb[2 - idx]
+    return out_images
+
+
+def color_normalization(images, mean, stddev):
+    """transform.py:476-517: (x - mean[idx]) / stddev[idx] by channel position."""
+    if images.dim() not in (3, 4):
+        raise NotImplementedError(f"Unsupported dimension {images.dim()}")
+    assert len(mean) == images.shape[images.dim() - 3], "channel mean not computed properly"
+    assert len(stddev) == images.shape[images.dim() - 3], "channel stddev not computed properly"
+    out_images = torch.zeros_like(images)
+    for idx in range(len(mean)):
+        if images.dim() == 3:
+            out_images[idx] = (images[idx] - mean[idx]) / stddev[idx]
+        else:
+            out_images[:, idx] = (images[:, idx] - mean[idx]) / stddev[idx]
+    return out_images
+
+
+def color_plan(brightness, contrast, saturation, alphastd, eigval, eigvec):
+    """What color_jitter(brightness, contrast, saturation) followed by lighting_jitter(alphastd, eigval, eigvec) would do,
+    without touching a pixel: consumes exactly their draws in their order and returns the fields of a focus_clip_color
+    record -- op (kinds 0 brightness, 1 contrast, 2 saturation in the applied order), alpha (1 + the op's uniform) and shift
+    BY BGR POSITION (position idx gets rgb[2 - idx]; zeros for alphastd == 0).  brightness = contrast = saturation = 0 plans
+    no op and draws nothing for them (the PCA-only configuration)."""
+    kinds = [k for k, var in ((0, brightness), (1, contrast), (2, saturation)) if var != 0]
+    var = {0: brightness, 1: contrast, 2: saturation}
+    op, alpha = [], []
+    if kinds:
+        order = np.random.permutation(np.arange(len(kinds)))
+        for idx in range(len(kinds)):
+            k = kinds[order[idx]]
+            op.append(k)
+            alpha.append(1.0 + np.random.uniform(-var[k], var[k]))
+    shift = [0.0, 0.0, 0.0]
+    if alphastd != 0:
+        rgb = _pca_rgb(alphastd, eigval, eigvec)
+        shift = [float(rgb[2 - idx]) for idx in range(3)]
+    return dict(op=op, alpha=alpha, shift=shift)

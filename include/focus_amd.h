@@ -780,6 +780,54 @@ int focus_clip_sample(const focus_clip_item* items, int n_clips, int T, int out_
                       int64_t sb, int64_t sc, int64_t st, const float* mean, const float* std, int reverse, int dtype,
                       void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Clip sampling with a colour stage (clip_color.hip): the AVA front end (ava_dataset.py:255-365 with
+ * AVA.IMG_PROC_BACKEND "pytorch"; transform.py:297-517: color_jitter, lighting_jitter, color_normalization).  Descriptors,
+ * taps, output addressing (sb, sc, st) and dtypes are focus_clip_sample's.  Between /255 and the normalisation every clip
+ * runs the ops of its focus_clip_color record, in the record's order; per pixel, x[c'] by SOURCE channel c':
+ *     x[c'] = v[c'] / 255                                                  (v: focus_clip_sample's bilinear value)
+ *     for i < n_ops:   a = alpha[i]
+ *         FOCUS_COLOR_BRIGHTNESS   x[c'] = x[c'] * a
+ *         FOCUS_COLOR_SATURATION   x[c'] = x[c'] * a + g * (1 - a),    g = sum_c' gray_w[c'] * x[c']  of this pixel, now
+ *         FOCUS_COLOR_CONTRAST     x[c'] = x[c'] * a + m_t * (1 - a),  m_t = frame_mean[b*T + t]
+ *     x[c'] += shift[c']                                                   (the PCA lighting shift; 0 = none)
+ *     out[b*sb + c*sc + t*st + y*out_w + x] = (x[c'] - mean[c']) / std[c'],   c' = reverse ? 2-c : c
+ * m_t is the mean over the out_h x out_w output window of frame t ALONE of the grey g of the pixel as it stands when
+ * contrast runs: resampled, windowed, mirrored, and after the ops listed before contrast.  Nothing is clamped.  gray_w,
+ * shift, mean and std are indexed by the source channel (a BGR source: gray_w = {0.114, 0.587, 0.299}).  Every kind occurs
+ * at most once in a record and alpha / shift are finite (focus_amd.ops.clip_sample_color raises ValueError otherwise; the
+ * kernels read n_ops clamped to 0..3 and treat an unknown kind as saturation).
+ *
+ * focus_clip_gray_mean writes frame_mean[n_clips * T] (fp32): m_t for a clip whose ops contain contrast, 0 for every other
+ * clip.  It is a reduction with a fixed order and no floating-point atomics (8 pixels per thread in x order, a 64-lane
+ * butterfly, the block's four waves in order, one partial per block in the workspace, the partials in block order by the
+ * block that arrives last -- told by an integer ticket), so the same arguments give the same bits.  The workspace is
+ * caller-owned, 4-byte aligned, at least focus_clip_color_workspace_bytes(...) long (0 for an empty or refused shape),
+ * needs no initialisation and holds nothing between calls.  A batch without any contrast op needs no call at all:
+ * focus_clip_sample_color reads frame_mean only for clips with contrast.  focus_clip_sample_color has no workspace and no
+ * atomics.  `colors`: DEVICE array of n_clips records; gray_w, mean, std: HOST pointers to 3 floats, read before return.
+ *
+ * Status, judged in this order before any launch (a refused call writes nothing): FOCUS_ERR_NULL (any pointer; the
+ * workspace too); FOCUS_OK without a launch for n_clips <= 0 or T <= 0; FOCUS_ERR_SHAPE (as focus_clip_sample);
+ * focus_clip_gray_mean then FOCUS_ERR_ALIGN (frame_mean or workspace not 4-byte aligned) and FOCUS_ERR_WORKSPACE
+ * (workspace_bytes too small); focus_clip_sample_color then FOCUS_ERR_DTYPE.
+ * ----------------------------------------------------------------------------------------------*/
+enum focus_color_op { FOCUS_COLOR_BRIGHTNESS = 0, FOCUS_COLOR_CONTRAST = 1, FOCUS_COLOR_SATURATION = 2 };
+typedef struct focus_clip_color {
+    int32_t n_ops;
+    int32_t op[3];       /* 0..3 ops, applied in this order, each kind at most once */
+    float alpha[3];      /* blend weight of op[i] */
+    float shift[3];      /* added after the ops, by source channel */
+} focus_clip_color;
+size_t focus_clip_color_workspace_bytes(int n_clips, int T, int out_h, int out_w);
+int focus_clip_gray_mean(const focus_clip_item* items, const focus_clip_color* colors, int n_clips, int T, int out_h,
+                         int out_w, const float* gray_w, float* frame_mean, void* workspace, size_t workspace_bytes,
+                         void* stream);
+int focus_clip_sample_color(const focus_clip_item* items, const focus_clip_color* colors, const float* frame_mean,
+                            int n_clips, int T, int out_h, int out_w, void* out, int64_t sb, int64_t sc, int64_t st,
+                            const float* mean, const float* std, const float* gray_w, int reverse, int dtype,
+                            void* stream);
+
 /* -------------------------------------------------------------------------------------------------
  * Mixup / CutMix of a batch of clips and the soft-target loss that goes with them (mixup.hip; datasets/mixup.py:40-192 and
  * losses.py:15-36 of the reference).  Sample i of the batch is always paired with sample B-1-i (x.flip(0)).  r() below is
