@@ -65,6 +65,16 @@ class OptimHyper(ctypes.Structure):
                 ("nesterov", ctypes.c_int32), ("write_clipped_grads", ctypes.c_int32), ("pad_", ctypes.c_int32)]
 
 
+POOL_CONV, POOL_MAX, POOL_AVG = 0, 1, 2
+
+
+class TokenPoolDesc(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_int32) for n in ("B", "T", "H", "W", "C", "head_dim", "cls")] +
+                [("k", ctypes.c_int32 * 3), ("s", ctypes.c_int32 * 3), ("p", ctypes.c_int32 * 3),
+                 ("mode", ctypes.c_int32), ("dtype", ctypes.c_int32),
+                 ("x_batch_stride", ctypes.c_int64), ("x_row_stride", ctypes.c_int64)])
+
+
 _CTYPE = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64,
           "size_t": ctypes.c_size_t, "float": ctypes.c_float, "double": ctypes.c_double}
 

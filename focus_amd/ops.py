@@ -3873,3 +3873,183 @@ def voc_average_precision(scores, bytes_, n_gt, total_gt):
         _lib.check(L.focus_voc_ap(_p(scores), _dt(scores), scores.stride(0) if N > 1 else C, _p(bytes_), C, N, C, _p(n_gt),
                                   total_gt, _p(ap), _p(summary), _p(flag), _p(ws), nbytes, _stream()), "voc_ap")
     return ap, summary, flag
+
+
+# --------------------------------------------------------------------------------------------------
+# Pooling attention in token layout (csrc/token_pool.hip): the attention_pool of MViT without its permutes
+# --------------------------------------------------------------------------------------------------
+_POOL_MODES = {"conv": _lib.POOL_CONV, "max": _lib.POOL_MAX, "avg": _lib.POOL_AVG}
+
+
+def _triple(v):
+    if isinstance(v, int):
+        return (v, v, v)
+    v = tuple(int(a) for a in v)
+    if len(v) != 3:
+        raise ValueError("focus_amd: a pooling window takes 3 extents (t, h, w), got %s" % (v,))
+    return v
+
+
+def _norm_parts(norm):
+    """None, an nn.LayerNorm-like module or (gamma, beta, eps) -> (gamma, beta, eps) or (None, None, 0.0)."""
+    if norm is None:
+        return None, None, 0.0
+    if isinstance(norm, (tuple, list)):
+        return norm[0], norm[1], float(norm[2])
+    return norm.weight, norm.bias, float(norm.eps)
+
+
+def token_pool_ok(x, head_dim, mode, kernel, stride, padding, norm, weight=None):
+    """True when ops.token_pool takes this call: x a device [B, N, C] fp32 / bf16 row view with unit column stride and
+    16-byte aligned rows, head_dim % 8 == 0 dividing C <= 4096 (<= 128 in conv mode or with a norm), windows 1..7, strides
+    1..8, padding below the window (a max window of at most 127 taps), fp32 dense norm parameters and conv weight."""
+    if not (torch.is_tensor(x) and x.is_cuda):
+        return False
+    gamma, beta, _ = _norm_parts(norm)
+    if any(t is not None and not t.is_cuda for t in (gamma, beta, weight)):
+        return False
+    return _token_pool_limits_ok(x, head_dim, mode, kernel, stride, padding, norm, weight)
+
+
+def _token_pool_limits_ok(x, head_dim, mode, kernel, stride, padding, norm, weight=None):
+    """token_pool_ok without its device test: shapes, types, strides and the kernels' limits."""
+    if not (x.dim() == 3 and x.dtype in (torch.float32, torch.bfloat16)):
+        return False
+    if mode not in _POOL_MODES:
+        return False
+    try:
+        k, s, p = _triple(kernel), _triple(stride), _triple(padding)
+    except (TypeError, ValueError):
+        return False
+    B, N, C = x.shape
+    head_dim = int(head_dim)
+    if head_dim < 8 or head_dim % 8 or C % head_dim or C > 4096 or x.numel() >= 2 ** 31:
+        return False
+    gamma, beta, _ = _norm_parts(norm)
+    if (mode == "conv" or gamma is not None) and head_dim > 128:
+        return False
+    if any(not 1 <= a <= 7 for a in k) or any(not 1 <= a <= 8 for a in s) or any(not 0 <= a < b for a, b in zip(p, k)):
+        return False
+    if mode == "max" and k[0] * k[1] * k[2] > 127:
+        return False
+    a = 16 // x.element_size()
+    if B > 0 and N > 0 and (x.stride(2) != 1 or x.stride(1) < C or x.stride(1) % a or x.stride(0) % a or x.data_ptr() % 16):
+        return False
+    for t in (gamma, beta, weight):
+        if t is not None and not (t.dtype == torch.float32 and t.is_contiguous()):
+            return False
+    if (gamma is None) != (beta is None) or (gamma is not None and (gamma.numel() != head_dim or beta.numel() != head_dim)):
+        return False
+    if mode == "conv" and weight is not None and weight.numel() != head_dim * k[0] * k[1] * k[2]:
+        return False
+    return True
+
+
+def _pool_desc(x, shape, thw, mode, k, s, p, cls, head_dim, dt):
+    """The descriptor of a call; x (None: dense) gives the strides of the input view."""
+    B, N, C = shape
+    d = _lib.TokenPoolDesc()
+    d.B, d.T, d.H, d.W, d.C, d.head_dim, d.cls = B, thw[0], thw[1], thw[2], C, head_dim, cls
+    for i in range(3):
+        d.k[i], d.s[i], d.p[i] = k[i], s[i], p[i]
+    d.mode, d.dtype = mode, dt
+    d.x_batch_stride, d.x_row_stride = (x.stride(0), x.stride(1)) if x is not None and B > 0 and N > 0 else (N * C, C)
+    return d
+
+
+class _TokenPoolFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, gamma, beta, cfg):
+        thw, thw_out, mode, k, s, p, cls, head_dim, eps, keep = cfg
+        B, N, C = x.shape
+        rows_out = cls + thw_out[0] * thw_out[1] * thw_out[2]
+        heads = C // head_dim
+        dev = x.device
+        d = _pool_desc(x, x.shape, thw, mode, k, s, p, cls, head_dim, _dt(x))
+        y = torch.empty(B, rows_out, C, device=dev, dtype=x.dtype)
+        norm = gamma is not None
+        pooled = mean = rstd = idx = None
+        if norm and keep:
+            pooled = torch.empty_like(y)
+            mean = torch.empty(B * rows_out * heads, device=dev, dtype=torch.float32)
+            rstd = torch.empty_like(mean)
+        if mode == _lib.POOL_MAX:
+            idx = torch.empty(B, rows_out, C, device=dev, dtype=torch.int8)
+        _lib.check(_lib.lib().focus_token_pool_fwd(ctypes.byref(d), _p(x), _p(weight), _p(gamma), _p(beta), eps, _p(y), _p(pooled),
+                                                   _p(mean), _p(rstd), _p(idx), _stream()), "token_pool_fwd")
+        if keep:
+            ctx.save_for_backward(x if (mode == _lib.POOL_CONV and ctx.needs_input_grad[1]) else None, weight, idx,
+                                  pooled, mean, rstd, gamma)
+            ctx.cfg = cfg
+            ctx.x_meta = (tuple(x.shape), x.dtype)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight, idx, pooled, mean, rstd, gamma = ctx.saved_tensors
+        thw, thw_out, mode, k, s, p, cls, head_dim, eps, _ = ctx.cfg
+        (B, N, C), dtype = ctx.x_meta
+        L = _lib.lib()
+        dev = dy.device
+        if dy.dtype != dtype:
+            dy = dy.to(dtype)
+        if not dy.is_contiguous():
+            dy = dy.contiguous()
+        dg = db = None
+        dp = dy
+        if gamma is not None:
+            # the per-head LayerNorm backward: the existing kernel on the [B*rows*heads, head_dim] view of the pooled rows
+            rows = mean.shape[0]
+            dp = torch.empty_like(pooled)
+            dg = torch.empty(head_dim, device=dev, dtype=torch.float32)
+            db = torch.empty(head_dim, device=dev, dtype=torch.float32)
+            partial = torch.empty(2, L.focus_layernorm_bwd_blocks(rows), head_dim, device=dev, dtype=torch.float32)
+            _lib.check(L.focus_layernorm_bwd(_p(dy), _p(pooled), _p(gamma), _p(mean), _p(rstd), None, _p(dp), _p(dg), _p(db),
+                                             _p(partial), rows, head_dim, _dt(pooled), _stream()), "layernorm_bwd")
+        want_dx = ctx.needs_input_grad[0]
+        want_dw = mode == _lib.POOL_CONV and ctx.needs_input_grad[1]
+        dx = dw = ws = None
+        nbytes = 0
+        if want_dx:
+            dx = torch.empty(B, N, C, device=dev, dtype=dtype)
+        if want_dx or want_dw:
+            d = _pool_desc(x if want_dw else None, (B, N, C), thw, mode, k, s, p, cls, head_dim, _dt(dp))
+            if want_dw:
+                dw = torch.empty(weight.shape, device=dev, dtype=torch.float32)
+                nbytes = L.focus_token_pool_workspace_bytes(ctypes.byref(d))
+                ws = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
+            _lib.check(L.focus_token_pool_bwd(ctypes.byref(d), _p(dp), _p(x) if want_dw else None, _p(weight), _p(idx), _p(dx),
+                                              _p(dw), _p(ws), nbytes, _stream()), "token_pool_bwd")
+        return dx, dw, dg, db, None
+
+
+def token_pool(x, thw, mode, weight, kernel, stride, padding, has_cls, head_dim, norm=None):
+    """attention_pool in token layout on the HIP kernels: x [B, cls + T*H*W, C] rows (heads = column blocks of head_dim; a
+    strided row view is read in place) -> (y [B, cls + T'*H'*W', C], [T', H', W']).  mode 'conv' (weight: the depth-wise
+    Conv3d.weight [head_dim, 1, kt, kh, kw], fp32, no bias), 'max' or 'avg' (count_include_pad).  norm: None, an nn.LayerNorm
+    over head_dim or (gamma, beta, eps): fused per head, from the un-rounded fp32 pooled values, the cls row included.
+    Gradients go to x, weight, gamma and beta; under torch.no_grad() nothing is kept.  No CPU fallback."""
+    gamma, beta, eps = _norm_parts(norm)
+    _need_gpu(x, weight, gamma, beta)
+    if mode not in _POOL_MODES:
+        raise ValueError("focus_amd: token_pool mode is 'conv', 'max' or 'avg' (got %r)" % (mode,))
+    k, s, p = _triple(kernel), _triple(stride), _triple(padding)
+    thw = [int(a) for a in thw]
+    cls = 1 if has_cls else 0
+    if x.dim() != 3 or x.shape[1] != cls + thw[0] * thw[1] * thw[2]:
+        raise RuntimeError("focus_amd: token_pool takes [B, %d + T*H*W, C] rows for the grid %s (got %s)" % (cls, thw, tuple(x.shape)))
+    if mode == "conv":
+        if weight is None or weight.dtype != torch.float32 or not weight.is_contiguous() or \
+                weight.numel() != int(head_dim) * k[0] * k[1] * k[2]:
+            raise RuntimeError("focus_amd: token_pool in conv mode takes a dense fp32 weight [head_dim, 1, kt, kh, kw]")
+    else:
+        weight = None
+    for t in (gamma, beta):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != int(head_dim)):
+            raise RuntimeError("focus_amd: token_pool's norm parameters are dense fp32 vectors of head_dim")
+    if x.shape[0] > 0 and x.stride(2) != 1:
+        x = x.contiguous()
+    thw_out = [(thw[i] + 2 * p[i] - k[i]) // s[i] + 1 for i in range(3)]
+    keep = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, weight, gamma, beta))
+    cfg = (tuple(thw), tuple(thw_out), _POOL_MODES[mode], k, s, p, cls, int(head_dim), eps, keep)
+    return _TokenPoolFn.apply(x, weight, gamma, beta, cfg), thw_out

@@ -141,9 +141,46 @@ class TrajectoryAttentionBlock(nn.Module):
 
 # --------------------------------------------------------------------------------------------------
 # Multiscale (pooling) attention: attention.py:16-352.  Linear / LayerNorm / Mlp / the attention products run on the HIP
-# kernels (ops.linear, ops.layer_norm, ops.mlp, ops.small_attention or ops.flash_attention); the pooling operators
-# themselves -- depth-wise Conv3d, MaxPool3d, AvgPool3d -- stay with ATen / MIOpen in fp32, like the dVAE convolutions.
+# kernels (ops.linear, ops.layer_norm, ops.mlp, ops.small_attention or ops.flash_attention), and so do the pooling operators:
+# the modules below keep q, k, v as [B, N, C] rows and pool them in that layout (ops.token_pool, csrc/token_pool.hip: the
+# depth-wise Conv3d / MaxPool3d / AvgPool3d over neighbouring rows with the per-head LayerNorm fused).  attention_pool is the
+# reference's function through ATen, kept for what ops.token_pool_ok refuses (CPU tensors, head dims above 128, windows
+# outside the kernels' limits) and for other callers.
 # --------------------------------------------------------------------------------------------------
+def _pool_spec(pool):
+    """(mode, weight, kernel, stride, padding) of a pooling module the token kernels can stand in for, else None."""
+    if isinstance(pool, nn.Conv3d):
+        if pool.bias is not None or pool.groups != pool.in_channels or pool.in_channels != pool.out_channels or \
+                tuple(pool.dilation) != (1, 1, 1) or pool.padding_mode != "zeros" or isinstance(pool.padding, str):
+            return None
+        return "conv", pool.weight, pool.kernel_size, pool.stride, pool.padding
+    if isinstance(pool, nn.MaxPool3d):
+        if pool.ceil_mode or pool.return_indices or pool.dilation not in (1, (1, 1, 1)):
+            return None
+        return "max", None, pool.kernel_size, pool.stride, pool.padding
+    if isinstance(pool, nn.AvgPool3d):
+        if pool.ceil_mode or not pool.count_include_pad or pool.divisor_override is not None:
+            return None
+        return "avg", None, pool.kernel_size, pool.stride, pool.padding
+    return None
+
+
+def pool_rows(x, pool, thw_shape, has_cls_embed, norm, num_heads):
+    """attention_pool on [B, N, C] rows whose columns are num_heads heads: the HIP kernels where ops.token_pool_ok takes the
+    call, else today's route through ATen (heads split off, attention_pool, heads folded back).  -> ([B, N', C], thw)."""
+    if pool is None:
+        return x, thw_shape
+    B, N, C = x.shape
+    spec = _pool_spec(pool)
+    if spec is not None:
+        mode, weight, kernel, stride, padding = spec
+        if ops.token_pool_ok(x, C // num_heads, mode, kernel, stride, padding, norm, weight):
+            return ops.token_pool(x, thw_shape, mode, weight, kernel, stride, padding, has_cls_embed, C // num_heads, norm)
+    t = x.reshape(B, N, num_heads, -1).permute(0, 2, 1, 3)
+    t, thw = attention_pool(t, pool, thw_shape, has_cls_embed, norm)
+    return t.permute(0, 2, 1, 3).reshape(B, -1, C), thw
+
+
 def attention_pool(tensor, pool, thw_shape, has_cls_embed=True, norm=None):
     """attention.py:16-50: [B, heads, L, C] (or [B, L, C]) -> pooled over the (T, H, W) grid, cls token passed around."""
     if pool is None:
@@ -217,24 +254,19 @@ class MultiScaleAttention(nn.Module):
         else:
             raise NotImplementedError("Unsupported model %s" % mode)
 
-    def _heads(self, t, B, n):
-        return t.reshape(B, n, self.num_heads, -1).permute(0, 2, 1, 3)
-
     def forward(self, x, thw_shape):
         B, N, C = x.shape
         if self.pool_first:
-            q = k = v = self._heads(x, B, N)
+            q = k = v = x
         else:
-            q = self._heads(ops.linear(x, self.q.weight, self.q.bias), B, N)
-            k = self._heads(ops.linear(x, self.k.weight, self.k.bias), B, N)
-            v = self._heads(ops.linear(x, self.v.weight, self.v.bias), B, N)
-        q, q_shape = attention_pool(q, self.pool_q, thw_shape, self.has_cls_embed, getattr(self, "norm_q", None))
-        k, k_shape = attention_pool(k, self.pool_k, thw_shape, self.has_cls_embed, getattr(self, "norm_k", None))
-        v, v_shape = attention_pool(v, self.pool_v, thw_shape, self.has_cls_embed, getattr(self, "norm_v", None))
-        # back to [B, n, C] rows: the layout the attention kernels read (heads = column blocks)
-        q = q.permute(0, 2, 1, 3).reshape(B, -1, C)
-        k = k.permute(0, 2, 1, 3).reshape(B, -1, C)
-        v = v.permute(0, 2, 1, 3).reshape(B, -1, C)
+            q = ops.linear(x, self.q.weight, self.q.bias)
+            k = ops.linear(x, self.k.weight, self.k.bias)
+            v = ops.linear(x, self.v.weight, self.v.bias)
+        # q, k, v stay [B, n, C] rows: the layout the pooling and the attention kernels read (heads = column blocks)
+        h, cls = self.num_heads, self.has_cls_embed
+        q, q_shape = pool_rows(q, self.pool_q, thw_shape, cls, getattr(self, "norm_q", None), h)
+        k, k_shape = pool_rows(k, self.pool_k, thw_shape, cls, getattr(self, "norm_k", None), h)
+        v, v_shape = pool_rows(v, self.pool_v, thw_shape, cls, getattr(self, "norm_v", None), h)
         if self.pool_first:
             q = ops.linear(q, self.q.weight, self.q.bias)
             k = ops.linear(k, self.k.weight, self.k.bias)
@@ -282,7 +314,7 @@ class MultiScaleBlock(nn.Module):
     def forward(self, x, metadata, thw_shape):
         n1, n2 = self.norm1, self.norm2
         x_block, thw_shape_new = self.attn(ops.layer_norm(x, n1.weight, n1.bias, n1.eps), thw_shape)
-        x_res, _ = attention_pool(x, self.pool_skip, thw_shape, has_cls_embed=self.has_cls_embed)
+        x_res, _ = pool_rows(x, self.pool_skip, thw_shape, self.has_cls_embed, None, 1)
         x = x_res + self.drop_path(x_block)
         x_norm = ops.layer_norm(x, n2.weight, n2.bias, n2.eps)
         if self.dim != self.dim_out:

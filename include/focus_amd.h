@@ -1225,6 +1225,61 @@ int focus_voc_ap(const void* scores, int dtype, int64_t lds, const uint8_t* byte
                  const int64_t* n_gt, int64_t total_gt, double* ap, double* summary, int32_t* flag, void* workspace,
                  size_t workspace_bytes, void* stream);
 
+/* -------------------------------------------------------------------------------------------------
+ * Pooling attention in token layout (token_pool.hip; attention.py:16-50, the attention_pool of MViT: a depth-wise Conv3d,
+ * MaxPool3d or AvgPool3d over the (T, H, W) grid of the tokens, then a LayerNorm per head).
+ *
+ * x is [B, cls + T*H*W, C] rows (sample stride x_batch_stride, row stride x_row_stride, in elements: a strided view is read in
+ * place); the columns are C / head_dim heads of head_dim.  The row of grid cell (t, h, w) is cls + (t*H + h)*W + w; with
+ * cls == 1 row 0 passes to output row 0 unpooled.  Output extents o = (i + 2p - k) / s + 1 (floor), output rows
+ * cls + ot*oh*ow per sample; every output is dense.  k, s, p are in (t, h, w) order; tap = (kt*kh_ + kh)*kw_ + kw.
+ *   FOCUS_POOL_CONV  y[c] = sum over the in-bounds taps of w[c % head_dim][tap] * x[c], fp32 in tap order; w is fp32
+ *                    [head_dim, kt*kh*kw] (a dense Conv3d.weight [head_dim, 1, kt, kh, kw] as it stands); no bias.
+ *   FOCUS_POOL_AVG   the sum over the in-bounds taps divided by kt*kh*kw (count_include_pad: padded taps count).
+ *   FOCUS_POOL_MAX   the maximum over the in-bounds taps, a NaN counting as a maximum; idx [B, rows_out, C] int8 holds the
+ *                    tap of the FIRST maximum in (t, h, w) order (ATen's rule); the cls row holds -1.
+ * gamma, beta (both or neither; fp32 [head_dim]): every output row, the cls row included, is normalised per head_dim-wide
+ *   column group from the un-rounded fp32 pooled values (biased variance, eps inside the root) -> y; the forward then also
+ *   writes the pre-norm rows to `pooled` in `dtype` and mean, rstd fp32 [B*rows_out*heads]: the arguments of
+ *   focus_layernorm_bwd with `pooled` viewed as [B*rows_out*heads, head_dim].  pooled, mean, rstd: all three or none (none: a forward
+ *   that keeps nothing for a backward).  Without gamma and beta y holds the pooled rows and the three are not written.
+ * focus_token_pool_bwd, from dpooled [B, rows_out, C] (after focus_layernorm_bwd where the forward normalised):
+ *   dx [B, rows_in, C] dense (may be NULL: not formed), a gather: every element is written once, the sum over the output
+ *     positions whose window covers the cell of w[c % head_dim][tap] * dpooled (max: dpooled where idx equals the tap; avg:
+ *     the sum / (kt*kh*kw)); the cls row receives dpooled row 0.
+ *   dw [head_dim, kt*kh*kw] fp32, OVERWRITTEN (conv only; may be NULL): the sum over samples, heads and output positions of
+ *     dpooled * x[tap].  Two stages in a fixed order: block partials in `workspace` (focus_token_pool_workspace_bytes), then
+ *     one reduction.  No atomics anywhere: the same inputs give the same bits.
+ * Host-only helpers: focus_token_pool_blocks(d, stage) is the number of workgroups of stage 0 (forward), 1 (forward with the
+ *   LayerNorm), 2 (dx) or the number of row blocks of the dw partials (3); 0 for a descriptor the kernels refuse.
+ *   focus_token_pool_workspace_bytes is 0 for such a descriptor and outside conv mode.
+ *
+ * Limits: head_dim % 8 == 0, head_dim >= 8, C % head_dim == 0, C <= 4096; head_dim <= 128 in conv mode or with the
+ *   LayerNorm; k in 1..7, s in 1..8, 0 <= p < k; kt*kh*kw <= 127 in max mode (the tap is an int8); every extent >= 1 and every
+ *   output extent >= 1; B*rows*C < 2^31 for the input and the output; x_row_stride >= C.
+ * Status, judged in this order before any launch (a refused call writes nothing): FOCUS_ERR_NULL (d); FOCUS_ERR_SHAPE (the
+ *   limits above; B < 0; cls outside {0, 1}; an unknown mode; a negative batch stride; backward: dw outside conv mode);
+ *   FOCUS_ERR_DTYPE (neither fp32 nor bf16); FOCUS_OK without a launch for B == 0; FOCUS_ERR_NULL (forward: x, y; w in conv
+ *   mode; idx in max mode; gamma without beta or the reverse; some but not all of pooled, mean, rstd.  backward: dpooled; both
+ *   dx and dw; with dx, w in conv mode and idx in max mode; with dw, x and workspace); FOCUS_ERR_ALIGN (a pointer not 16-byte
+ *   aligned, or a stride of x that is not a multiple of 16 bytes); FOCUS_ERR_WORKSPACE (backward with dw: workspace_bytes
+ *   below focus_token_pool_workspace_bytes).
+ * ----------------------------------------------------------------------------------------------*/
+enum focus_pool_mode { FOCUS_POOL_CONV = 0, FOCUS_POOL_MAX = 1, FOCUS_POOL_AVG = 2 };
+typedef struct focus_token_pool_desc {
+    int32_t B, T, H, W, C, head_dim, cls;
+    int32_t k[3], s[3], p[3];
+    int32_t mode, dtype;
+    int64_t x_batch_stride, x_row_stride;
+} focus_token_pool_desc;
+int focus_token_pool_blocks(const focus_token_pool_desc* d, int stage);
+size_t focus_token_pool_workspace_bytes(const focus_token_pool_desc* d);
+int focus_token_pool_fwd(const focus_token_pool_desc* d, const void* x, const float* w, const float* gamma,
+                         const float* beta, float eps, void* y, void* pooled, float* mean, float* rstd, void* idx,
+                         void* stream);
+int focus_token_pool_bwd(const focus_token_pool_desc* d, const void* dpooled, const void* x, const float* w,
+                         const void* idx, void* dx, float* dw, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
